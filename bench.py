@@ -13,7 +13,10 @@ config 3 of BASELINE.json, 65,536 x 1 MiB blocks (64 GiB) per GPU (`--config 3a`
 N > 1: one process per GPU, each rank checksums its own shard; no data-path collective.  The ranks come from torchrun,
 or -- `bench.py --gpus N` with no WORLD_SIZE in the environment -- from bench.py itself (launch_ranks), over RCCL.
 
-Outside the timed region: RCCL all-gather of every rank's u32 results (4 B per block) and a check of EVERY block of
+A plain run sets up, warms up, times the steps, gathers every rank's u32 results (4 B per block, RCCL), writes them
+with --dump-outputs DIR (DIR/crc32c.npy; with --form verify also first_bad.npy and nbad.npy) and prints the line.
+
+With --full, outside the timed region: the per-launch kernel timing pass of a split batch; a check of EVERY block of
 every rank against the reference's whole-batch outputs (tests/golden/full_cfg*.u32 per block at up to 8 ranks;
 config 4 beyond its first 2^20 blocks by the reference's per-rank digests, full_cfg4_ranks.json -- all computed by the
 compiled util/crc32c.cc); the read-only streaming ceiling; the host
@@ -410,7 +413,7 @@ def check_results(plan_all, results, oracle):
         k = plan.count
         gold = None
         if plan.golden:
-            gold = gold_cache.setdefault(plan.golden, np.fromfile(os.path.join(GOLDEN, plan.golden), dtype="<u4"))
+            gold = gold_cache.setdefault(plan.golden, W.read_u32(os.path.join(GOLDEN, plan.golden)))
         for p, (base, ib) in enumerate(plan.passes):
             got = res[p * k:(p + 1) * k]
             total += k
@@ -435,6 +438,21 @@ def check_results(plan_all, results, oracle):
             "blocks_checked_vs_reference_digest": by_digest, "blocks_sampled_vs_oracle": sampled,
             "every_block_checked": checked + by_digest == total, "mismatches": mism,
             "mismatching_digest_ranges": bad_ranges}
+
+
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy in float64 (exact for u32 results and block counts).  Together
+    they stay under DUMP_MAX_BYTES: a longer array is cut to a fixed, seeded sample of its elements, in index order."""
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_MAX_BYTES // 8 // max(1, len(arrays)) - 64  # elements per array; the .npy header is < 512 B
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size > budget:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, budget, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
 
 
 def live_pmc_traffic(args, timeout_s=240):
@@ -583,6 +601,13 @@ def main():
     ap.add_argument("--pmc-json", default=None,
                     help="PMC summary of the same config (default profiles/pmc_cfg<config>.json, written by "
                          "kv-separate_amd/tools/pmc_summary.py from separate rocprofv3 --pmc passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the per-launch kernel "
+                         "timing pass, the check of every block against the reference's outputs, the read ceiling, "
+                         "the single-pass rates, the host round trip, the CPU baseline and the roofline traffic "
+                         "(--no-cpu, --roundtrip-gib 0 and --pmc-live off still switch single parts off)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ:
@@ -681,7 +706,7 @@ def main():
         ib = plan.passes[0][1]
         gold = None
         if plan.golden:
-            g = np.fromfile(os.path.join(GOLDEN, plan.golden), dtype="<u4")
+            g = W.read_u32(os.path.join(GOLDEN, plan.golden))
             if g.size >= ib + count:
                 gold = g[ib:ib + count]
         if gold is None:  # no reference words for this range (config 4 past its first 2^20 blocks): the batch form's
@@ -721,10 +746,10 @@ def main():
         # kernel-only time of the CRC kernel, HIP events on the stream it runs on.  A step of an unsplit batch is the
         # CRC kernel alone: under graph replay, one event pair around the timed region gives its average over the
         # back-to-back launches.  A split batch also runs planning and combine kernels, so its CRC kernel is timed
-        # with an event pair per launch over the same number of eager steps.
+        # with an event pair per launch over the same number of eager steps -- a pass of its own, so only with --full.
         ctx.get_timing()
         ctx.set_timing(True)
-        for _ in range(args.steps if args.launch == "graph" and not span_timing else 0):
+        for _ in range(args.steps if args.full and args.launch == "graph" and not span_timing else 0):
             crc(0, stream)
         torch.cuda.synchronize()
         # the timed steps as hipGraph replays: each captured step is a full pass of the hot path (planning kernels,
@@ -807,9 +832,10 @@ def main():
     total_useful = int(shard.sum_over_ranks(total_useful, dd, coll_dev))
     ms_per_step = elapsed * 1e3 / args.steps
     value = total_useful * args.steps / GIB / elapsed
-    kern_avg_ms = kern_ms / max(1, launches)
+    # no kernel time where no launch was timed on its own (a plain run of a split batch under graph replay)
+    kern_avg_ms = kern_ms / launches if launches and kern_ms > 0 else None
     kernel_name = ctx.kernel_name(count, max_len, useful)
-    achieved_gbps = useful / (kern_avg_ms * 1e-3) / 1e9
+    achieved_gbps = useful / (kern_avg_ms * 1e-3) / 1e9 if kern_avg_ms else None
     my_record = rank_record(rank, local, local, placement, kern_avg_ms, own, t_start, t_end,
                             useful * npass * args.steps, kernel_name, launch_bytes=useful)
 
@@ -833,7 +859,13 @@ def main():
         crcs = crcs.copy()
         crcs[crcs.size // 2] ^= np.uint32(1)
     results = shard.gather_results(crcs, dd, coll_dev)
-    digests = [shard.crc_of_crcs(r, kvsep.extend_host) for r in results]
+    if args.dump_outputs and rank == 0:
+        dumped = {"crc32c": np.concatenate(results) if results else crcs}  # every rank's blocks, in rank order
+        if verify:
+            dumped["first_bad"], dumped["nbad"] = np.array([verdict["first_bad"]]), np.array([verdict["nbad"]])
+        dump_outputs(args.dump_outputs, dumped)
+    full = args.full
+    digests = [shard.crc_of_crcs(r, kvsep.extend_host) for r in results] if full else None
 
     # The attainable read rate over the same allocation: stream_read_kernel, the fastest read-only pattern of
     # tools/hbm_probe.hip, over the batch's span.  From 8 GiB up, three eager launches timed by HIP events; below,
@@ -841,7 +873,9 @@ def main():
     # pair around the replay -- so the ceiling carries the same launch ramp and drain per launch (config 2: the
     # same-size streaming read).
     read_ceiling_gbps = ceiling_note = None
-    if span >= 8 * (1 << 30):
+    if not full:
+        pass
+    elif span >= 8 * (1 << 30):
         sink = torch.zeros(4, dtype=torch.int32, device=dev)
         ctx.stream_read(data.data_ptr(), span, sink, stream=stream)  # warm
         torch.cuda.synchronize()
@@ -885,7 +919,7 @@ def main():
     # read alike (profiles/round6/README.md, claim_pipeline_ab/rot_*: config 2 44.2 -> 48.0 us).  Small one-pass batch
     # forms only; reported beside the line's value, never as it.
     single_pass = None
-    if span and npass == 1 and not verify and span <= (1 << 30) and args.launch == "graph":
+    if full and span and npass == 1 and not verify and span <= (1 << 30) and args.launch == "graph":
         try:
             copies = [data] + [torch.empty_like(data) for _ in range(7)]
             for c in copies[1:]:
@@ -929,7 +963,7 @@ def main():
 
     parity = None
     cpu = None
-    if rank == 0:
+    if full and rank == 0:
         oracle = load_oracle()
         parity = check_results([Plan(args.config, world, r) for r in range(world)], results, oracle)
         parity["all_blocks_match"] = parity["mismatches"] == 0 and parity["mismatching_digest_ranges"] == 0
@@ -985,7 +1019,7 @@ def main():
     # Every rank runs the same collectives whatever fails locally, so a failure cannot leave a rank waiting.
     rt = None
     rt_ok = None
-    if args.roundtrip_gib > 0:
+    if full and args.roundtrip_gib > 0:
         state = None
         try:
             state = roundtrip_setup(ctx, int(args.roundtrip_gib * GIB))
@@ -1023,7 +1057,7 @@ def main():
     pmc_cfg = "3b" if args.config == "5" else args.config  # config 5's launches are config-3b launches
     if args.pmc_json is None:
         args.pmc_json = os.path.join(ROOT, "profiles", f"pmc_cfg{pmc_cfg}.json")
-    if os.path.exists(args.pmc_json):
+    if full and os.path.exists(args.pmc_json):
         try:
             pm = json.load(open(args.pmc_json))
             if pm.get("config") == pmc_cfg:
@@ -1034,7 +1068,8 @@ def main():
     # auto: at N = 1, and never when this process itself runs under a profiler (rocprofv3 exports ROCPROF_* to the
     # program it profiles; a nested profiler pass would fight it for the counters)
     under_profiler = any(k.startswith("ROCPROF") for k in os.environ)
-    if rank == 0 and (args.pmc_live == "on" or (args.pmc_live == "auto" and world == 1 and not under_profiler)):
+    if full and rank == 0 and (args.pmc_live == "on" or
+                               (args.pmc_live == "auto" and world == 1 and not under_profiler)):
         # the child allocates its own batch: free this one first (config 4 is 150 GiB of the 288)
         data = d_off = d_len = out = None  # noqa: F841
         torch.cuda.synchronize()
@@ -1056,6 +1091,7 @@ def main():
             "world_size": world,
             "backend": dist.get_backend() if dd else None,
             "steps": args.steps,
+            "full": full,
             "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 4),
             "launch": launch,
@@ -1068,23 +1104,26 @@ def main():
                        "bytes_per_gpu": useful * npass, "total_bytes": total_useful,
                        "piece_bytes": args.piece_kib * 1024 or kvsep.DEFAULT_PIECE_BYTES,
                        "parallelism": f"shard{world} (independent blocks per GPU, no data-path collective)"},
-            "roofline": {"bound": "hbm", "achieved": round(achieved_gbps, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved_gbps / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                         "traffic_source": traffic_src, "traffic_committed_profile": traffic_profile,
+            "roofline": {"bound": "hbm", "achieved": achieved_gbps and round(achieved_gbps, 1), "peak": HBM_PEAK_GBPS,
+                         "unit": "GB/s", "frac": achieved_gbps and round(achieved_gbps / HBM_PEAK_GBPS, 4),
+                         "traffic": traffic, "traffic_source": traffic_src,
+                         "traffic_committed_profile": traffic_profile,
                          "traffic_over_algorithmic": traffic and round(traffic / useful, 4),
-                         "kernel": kernel_name, "kernel_avg_ms": round(kern_avg_ms, 4), "kernel_timing": timing_note,
+                         "kernel": kernel_name, "kernel_avg_ms": kern_avg_ms and round(kern_avg_ms, 4),
+                         "kernel_timing": timing_note if kern_avg_ms else None,
                          "algorithmic_bytes_per_launch": useful},
             "cpu_baseline": cpu,
             "read_ceiling_GBps": read_ceiling_gbps and round(read_ceiling_gbps, 1),
             "read_ceiling_timing": ceiling_note,
-            "frac_of_read_ceiling": read_ceiling_gbps and round(achieved_gbps / read_ceiling_gbps, 4),
+            "frac_of_read_ceiling": read_ceiling_gbps and achieved_gbps and
+                                    round(achieved_gbps / read_ceiling_gbps, 4),
             "single_pass": single_pass,
             "host_roundtrip_GiBps": rt,
             "host_roundtrip_ranks": world if rt is not None else None,
             "host_roundtrip_parity": rt_ok,
             "parity": parity,
-            "parity_spot_check": bool(parity and parity["all_blocks_match"]),
-            "digests": [hex(d) for d in digests],
+            "parity_spot_check": None if parity is None else bool(parity["all_blocks_match"]),
+            "digests": digests and [hex(d) for d in digests],
             "per_rank": per_rank,
             "per_rank_summary": shard.rank_summary(per_rank, same_device=same_device),
             "form": args.form,

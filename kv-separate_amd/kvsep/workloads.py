@@ -23,6 +23,30 @@ ZIPF_CLASSES = 18                 # k in [0, 17]: len ~ U[32*2^k, min(32*2^(k+1)
 MAX_LEN = (4 << 20) + 1
 
 
+U32_PART_BYTES = 512 * 1024       # a stored u32 vector is kept as parts of this size (tests/golden/full_cfg*.u32.NN)
+
+
+def write_u32(path: str, a: np.ndarray) -> int:
+    """Store a u32 vector little-endian as path.00, path.01, ... of U32_PART_BYTES each -> the number of parts."""
+    a = np.ascontiguousarray(a, dtype="<u4")
+    per = U32_PART_BYTES // 4
+    parts = max(1, -(-a.size // per))
+    for k in range(parts):
+        a[k * per:(k + 1) * per].tofile(f"{path}.{k:02d}")
+    return parts
+
+
+def read_u32(path: str) -> np.ndarray:
+    """The u32 vector write_u32 stored under `path`: its parts path.00, path.01, ... in order."""
+    import os
+    parts = []
+    while os.path.exists(f"{path}.{len(parts):02d}"):
+        parts.append(np.fromfile(f"{path}.{len(parts):02d}", dtype="<u4"))
+    if not parts:
+        raise FileNotFoundError(f"{path}.00")
+    return np.concatenate(parts)
+
+
 def splitmix_words(seed: int, j: np.ndarray) -> np.ndarray:
     j = np.asarray(j, dtype=np.uint64)
     with np.errstate(over="ignore"):

@@ -28,6 +28,6 @@ for _ in range(reps):
     ctx.batch_device(data.data_ptr(), d_off, d_len, out, count=off.size, total_bytes=total, max_len=4096)
     ctx.stream_read(data.data_ptr(), total, sink)
 torch.cuda.synchronize()
-ref = np.fromfile(os.path.join(os.path.dirname(__file__), "..", "..", "tests", "golden", "full_cfg2.u32"), dtype="<u4")
+ref = W.read_u32(os.path.join(os.path.dirname(__file__), "..", "..", "tests", "golden", "full_cfg2.u32"))
 assert np.array_equal(out.cpu().numpy().view(np.uint32), ref[:off.size]), "config 2 CRCs differ from the reference"
 print("ok", ctx.kernel_name(off.size, 4096, total))

@@ -18,6 +18,7 @@ The files cover the GLOBAL batch bench.py builds at up to 8 ranks, so every bloc
                   per-block CRCs of the 8-rank batch (8 Mi blocks, 1.2 TiB) are 32 MiB, too much to commit, so the
                   file holds, for every (N, rank), the range [lo, hi) and crc_of_crcs -- the reference's
                   Extend(0, LE u32 CRCs of blocks lo..hi-1) (kvsep/shard.py crc_of_crcs) -- plus the xor of them.
+Each .u32 vector is stored as 512 KiB parts, <name>.00, <name>.01, ... (kvsep.workloads.write_u32 / read_u32).
 The seeds and stream offsets are the ones bench.py uses, so a bench run can be checked against these too.
 
   python3 tests/golden/make_fullsize_golden.py [--only full_cfg3a.u32 ...]
@@ -66,7 +67,7 @@ def cfg4_ranks(r, threads):
     goff = np.zeros(glen.size, np.uint64)
     goff[1:] = np.cumsum(glen[:-1], dtype=np.uint64)
     crcs = stream_batch(r, W.SEED + 2, 0, goff, glen, threads)
-    first = np.fromfile(os.path.join(HERE, "full_cfg4.u32"), dtype="<u4")
+    first = W.read_u32(os.path.join(HERE, "full_cfg4.u32"))
     assert np.array_equal(crcs[:first.size], first), "the 8-rank batch must extend config 4"
     out = {"seed": W.SEED + 2, "blocks_per_rank": W.CFG4_BLOCKS, "digest": "crc_of_crcs", "ranks": {}}
     for n in RANK_COUNTS:
@@ -119,7 +120,7 @@ def main():
                 json.dump(a, f, indent=1)
             print(f"{name}: written in {time.time() - t:.1f} s", flush=True)
         else:
-            a.astype("<u4").tofile(path)
+            W.write_u32(path, a)  # parts of W.U32_PART_BYTES: full_cfg*.u32.00, .01, ...
             print(f"{name}: {a.size} blocks in {time.time() - t:.1f} s", flush=True)
 
 

@@ -18,6 +18,7 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 import kvsep  # noqa: E402
 from kvsep import shard  # noqa: E402
+from kvsep import workloads as W  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
@@ -28,7 +29,7 @@ def _json():
 
 
 def _u32(name):
-    return np.fromfile(os.path.join(GOLDEN, name), dtype="<u4")
+    return W.read_u32(os.path.join(GOLDEN, name))
 
 
 @pytest.mark.parametrize("world", [1, 2, 4, 8])

@@ -31,7 +31,7 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def golden(name):
-    return np.fromfile(os.path.join(GOLDEN, name), dtype="<u4")
+    return W.read_u32(os.path.join(GOLDEN, name))
 
 
 def u64(a):

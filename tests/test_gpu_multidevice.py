@@ -67,7 +67,7 @@ def test_group_vlog_scan_like_gc(group, oracle):
     off, ln = W.cfg3_layout(vlog=True, count=96)
     span = int(off[-1] + ln[-1])
     img = splitmix64_bytes(span, W.SEED + 1, 0)
-    crc = np.fromfile(os.path.join(GOLDEN, "full_cfg5.u32"), dtype="<u4")[:96]  # the reference's CRCs
+    crc = W.read_u32(os.path.join(GOLDEN, "full_cfg5.u32"))[:96]  # the reference's CRCs
     for i in range(96):  # the stored headers a VlogWriter writes (db/value_log_writer.cc:57-60)
         h = int(off[i]) - 8
         img[h:h + 4] = np.frombuffer(kvsep.mask(int(crc[i])).to_bytes(4, "little"), np.uint8)
@@ -80,7 +80,7 @@ def test_group_vlog_scan_like_gc(group, oracle):
 def test_group_device_shards_vs_reference(group):
     """Device-resident shards of config 2 (the reference's full-batch CRCs): one shard per member."""
     off, ln = W.cfg2_layout()
-    ref = np.fromfile(os.path.join(GOLDEN, "full_cfg2.u32"), dtype="<u4")[:W.CFG2_BLOCKS]
+    ref = W.read_u32(os.path.join(GOLDEN, "full_cfg2.u32"))[:W.CFG2_BLOCKS]
     data = torch.empty(int(ln.sum()) + 64, dtype=torch.uint8, device=DEV)
     kvsep.fill_splitmix64(data.data_ptr(), int(ln.sum()), W.SEED, 0)
     b = kvsep.partition(ln, 2)
@@ -120,7 +120,7 @@ def test_group8_vlog_scan_bad_record_in_last_member(group8):
     off, ln = W.cfg3_layout(vlog=True, count=n)
     span = int(off[-1] + ln[-1])
     img = splitmix64_bytes(span, W.SEED + 1, 0)
-    crc = np.fromfile(os.path.join(GOLDEN, "full_cfg5.u32"), dtype="<u4")[:n]
+    crc = W.read_u32(os.path.join(GOLDEN, "full_cfg5.u32"))[:n]
     for i in range(n):
         h = int(off[i]) - 8
         img[h:h + 4] = np.frombuffer(kvsep.mask(int(crc[i])).to_bytes(4, "little"), np.uint8)
@@ -138,7 +138,7 @@ def test_group8_device_shards_index_base_vs_reference(group8):
     """All of config 2 (the reference's whole-batch CRCs) as eight device shards with index_base: results, and the
     global first_bad / nbad of stored words corrupted in members 2, 5 and 7."""
     off, ln = W.cfg2_layout()
-    ref = np.fromfile(os.path.join(GOLDEN, "full_cfg2.u32"), dtype="<u4")[:W.CFG2_BLOCKS]
+    ref = W.read_u32(os.path.join(GOLDEN, "full_cfg2.u32"))[:W.CFG2_BLOCKS]
     data = torch.empty(int(ln.sum()) + 64, dtype=torch.uint8, device=DEV)
     kvsep.fill_splitmix64(data.data_ptr(), int(ln.sum()), W.SEED, 0)
     b = kvsep.partition(ln, 8)
@@ -226,7 +226,7 @@ def _torchrun_bench(nproc, *bench_args, timeout=900):
     env = dict(os.environ, KVSEP_BENCH_SAME_DEVICE="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(nproc), "--no-cpu", "--roundtrip-gib", "0", *bench_args]
+           "--gpus", str(nproc), "--no-cpu", "--full", "--roundtrip-gib", "0", *bench_args]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -255,7 +255,7 @@ def test_bench_self_launch_two_ranks_config2():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "2", "--steps", "3", "--warmup",
-           "1", "--no-cpu", "--roundtrip-gib", "0"]
+           "1", "--no-cpu", "--full", "--roundtrip-gib", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -272,7 +272,7 @@ def test_bench_self_launch_eight_ranks_config2_every_block():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--config", "2", "--steps", "3", "--warmup",
-           "1", "--no-cpu", "--roundtrip-gib", "0"]
+           "1", "--no-cpu", "--full", "--roundtrip-gib", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -297,7 +297,7 @@ def test_two_ranks_host_round_trip_per_rank_records():
     env = dict(os.environ, KVSEP_BENCH_SAME_DEVICE="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-cpu",
-           "--config", "2", "--steps", "3", "--warmup", "1", "--roundtrip-gib", "0.25"]
+           "--config", "2", "--steps", "3", "--warmup", "1", "--full", "--roundtrip-gib", "0.25"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -329,7 +329,7 @@ def test_verify_form_config4_one_rank():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "KVSEP_BENCH_SAME_DEVICE"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "4", "--steps", "2", "--warmup", "1",
-           "--no-cpu", "--roundtrip-gib", "0", "--pmc-live", "off", "--form", "verify"]
+           "--no-cpu", "--full", "--roundtrip-gib", "0", "--pmc-live", "off", "--form", "verify"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

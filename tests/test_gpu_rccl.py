@@ -79,7 +79,7 @@ def test_bench_torchrun_one_rank_rccl():
     env = _env()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
            "127.0.0.1", "--master-port", env["MASTER_PORT"], os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config",
-           "2", "--steps", "4", "--warmup", "1", "--no-cpu", "--pmc-live", "off", "--roundtrip-gib", "0.25"]
+           "2", "--steps", "4", "--warmup", "1", "--no-cpu", "--pmc-live", "off", "--full", "--roundtrip-gib", "0.25"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -107,7 +107,7 @@ def test_bench_verify_form_one_rank_rccl():
     env = _env()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
            "127.0.0.1", "--master-port", env["MASTER_PORT"], os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config",
-           "2", "--steps", "4", "--warmup", "1", "--no-cpu", "--pmc-live", "off", "--roundtrip-gib", "0",
+           "2", "--steps", "4", "--warmup", "1", "--no-cpu", "--pmc-live", "off", "--full", "--roundtrip-gib", "0",
            "--form", "verify"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -124,7 +124,7 @@ def test_bench_wrong_result_exits_nonzero():
     env = _env()
     env["KVSEP_BENCH_CORRUPT_RESULT"] = "0"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "2", "--steps", "2", "--warmup", "1", "--no-cpu",
-           "--pmc-live", "off", "--roundtrip-gib", "0"]
+           "--pmc-live", "off", "--full", "--roundtrip-gib", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 1, (r.returncode, r.stderr[-3000:])
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -100,7 +100,7 @@ _GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _full(name):
-    return np.fromfile(os.path.join(_GOLDEN_DIR, name), dtype="<u4")
+    return W.read_u32(os.path.join(_GOLDEN_DIR, name))
 
 
 def test_fullsize_files_agree_with_the_small_fixtures(golden):
