@@ -143,7 +143,13 @@ const char* kvsep_crc32c_kernel_name(kvsep_crc32c_ctx* ctx, uint64_t count, uint
  * kernel.  Results are exact whatever the hints say: a block longer than max_len is checksummed whole by
  * the wide kernel or deferred by the narrow one, and an understated total_bytes makes the kernel fall back
  * to one work item per block.  count <= 2^32 - 1, and <= 2^31 - 1 when the batch is planned (max_len 0 or
- * above the piece size); else KVSEP_EINVAL. */
+ * above the piece size); else KVSEP_EINVAL.
+ * Memory touched (this form and the verify form below): the payload needs no padding -- a block may start on the
+ * first byte of a mapping and end on its last.  The kernels read only naturally aligned 16-B granules that hold at
+ * least one byte of a block of the batch (the cooperative kernel, reachable through kvsep_crc32c_ctx_set_kernel
+ * only: 128-B lines that do), so never a page no block touches.  A block with len[i] == 0 is never dereferenced,
+ * whatever off[i] is; out[i] = its init.  off, len, init (and expected_masked) are read for exactly `count`
+ * elements, out is written for exactly `count`; the payload is never written. */
 int kvsep_crc32c_batch_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, const uint64_t* off,
                               const uint64_t* len, const uint32_t* init, uint32_t* out, uint64_t count,
                               uint64_t total_bytes, uint64_t max_len);

@@ -31,20 +31,27 @@ class EmuError(RuntimeError):
 
 # ------------------------------------------------------------------------------------------------------------------
 class Memory:
-    """Sparse flat address space of byte regions."""
+    """Sparse flat address space of byte regions.  track: every region also keeps one read and one write mark per byte,
+    set by whatever goes through read() / write() -- the emulated scalar and vector loads, stores and atomics (an
+    atomic marks both); view() is the harness's own access and marks nothing.  Off (the default) costs nothing."""
 
-    def __init__(self):
+    def __init__(self, track: bool = False):
         self.regions = []  # (base, np.uint8 array)
+        self.marks = {} if track else None  # region base -> (read marks, write marks), one np.bool_ per byte
         self.next = 0x10000000
+        self.payload = None  # batch_memory: (guard region base, its size, payload address, payload size)
 
-    def alloc(self, nbytes: int, align: int = 256, data=None) -> int:
-        base = (self.next + align - 1) // align * align
+    def alloc(self, nbytes: int, align: int = 256, data=None, phase: int = 0, at: int = 0) -> int:
+        """A region of nbytes whose base is `phase` past a multiple of `align`; data is copied in at byte `at`."""
+        base = (self.next - phase + align - 1) // align * align + phase
         arr = np.zeros(max(1, nbytes), dtype=np.uint8)
         if data is not None:
             b = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else \
                 data.view(np.uint8).reshape(-1)
-            arr[:b.size] = b
+            arr[at:at + b.size] = b
         self.regions.append((base, arr))
+        if self.marks is not None:
+            self.marks[base] = (np.zeros(arr.size, dtype=bool), np.zeros(arr.size, dtype=bool))
         self.next = base + arr.size + 4096
         return base
 
@@ -56,10 +63,14 @@ class Memory:
 
     def read(self, addr: int, n: int) -> bytes:
         arr, o = self.find(addr, n)
+        if self.marks is not None:
+            self.marks[addr - o][0][o:o + n] = True
         return arr[o:o + n].tobytes()
 
     def write(self, addr: int, data: bytes):
         arr, o = self.find(addr, len(data))
+        if self.marks is not None:
+            self.marks[addr - o][1][o:o + len(data)] = True
         arr[o:o + len(data)] = np.frombuffer(data, dtype=np.uint8)
 
     def r32(self, addr):
@@ -71,6 +82,15 @@ class Memory:
     def view(self, addr: int, n: int) -> np.ndarray:
         arr, o = self.find(addr, n)
         return arr[o:o + n]
+
+    def peek64(self, addr: int) -> int:
+        """A 64-bit word as the harness reads it: no mark."""
+        return int(self.view(addr, 8).view(np.uint64)[0])
+
+    def touched(self, addr: int):
+        """(base, read marks, write marks) of the tracked region that holds addr."""
+        arr, o = self.find(addr, 1)
+        return (addr - o,) + self.marks[addr - o]
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -1069,18 +1089,42 @@ def launch(mem: Memory, asm: str, name: str, threads: int, lds_bytes: int, field
     return steps
 
 
+def launch_plain(mem: Memory, asm: str, name: str, threads: int, args: bytes, grid: int) -> int:
+    """Run every workgroup of a kernel with ordinary arguments (`args`: their kernarg image, a multiple of 8 bytes;
+    the hidden block counts and group sizes follow it, as for the PiecesArgs kernels)."""
+    assert len(args) % 8 == 0
+    ka = bytearray(args) + bytearray(256)
+    struct.pack_into("<III", ka, len(args), grid, 1, 1)
+    struct.pack_into("<HHH", ka, len(args) + 12, threads, 1, 1)
+    struct.pack_into("<H", ka, len(args) + 64, 1)
+    insns, labels = kernel_code(asm, name)
+    d_ka = mem.alloc(len(ka), data=bytes(ka))
+    return sum(Workgroup(mem, insns, labels, threads, group_segment_bytes(asm, name), d_ka, g).run()
+               for g in range(grid))
+
+
 SENTINEL = 0xDEADBEEF
 
 
-def batch_memory(data, off, ln, tabs: bytes, expect=None, last_of=None, shards: int = 1):
+def batch_memory(data, off, ln, tabs: bytes, expect=None, last_of=None, shards: int = 1, slack: int = 65536,
+                 guard: int = 0, skew: int | None = None, track: bool = False):
     """Device image of one batch call: payload, descriptors, results (sentinel-filled), tables, verify words.  The
     caller's result words start as a sentinel (the kernels must write them); the accumulators in their reset state,
     except with last_of = (wg, grid): every other workgroup of the grid counts as arrived already, so emulating that
     one workgroup is the last, publishing one (shards > 1: a two-level arrival, verify_publish<kShards>: the rest of
-    its shard on the shard word, the other shards' last workgroups on the final word)."""
+    its shard on the shard word, the other shards' last workgroups on the final word).
+    The payload's region is `guard` bytes, the payload, `slack` + `guard` bytes (mem.payload says where); with skew
+    (0..4095) the payload's first byte lies that far past a 4 KiB boundary.  track: every region keeps access marks
+    (Memory.touched).  The descriptor arrays are regions of exactly their size: a read past one is a bad address."""
     n = int(np.asarray(off).size)
-    mem = Memory()
-    f = {"base": mem.alloc(data.size + 65536, data=data), "off": mem.alloc(8 * n, data=np.asarray(off, np.uint64)),
+    mem = Memory(track)
+    if skew is None:
+        region = mem.alloc(guard + data.size + slack + guard, data=data, at=guard)
+    else:
+        region = mem.alloc(guard + data.size + slack + guard, align=4096, data=data, phase=(skew - guard) % 4096,
+                           at=guard)
+    mem.payload = (region, guard + data.size + slack + guard, region + guard, int(data.size))
+    f = {"base": region + guard, "off": mem.alloc(8 * n, data=np.asarray(off, np.uint64)),
          "len": mem.alloc(8 * n, data=np.asarray(ln, np.uint64)),
          "out": mem.alloc(4 * n, data=np.full(n, SENTINEL, np.uint32)), "count": n, "piece_bytes": 128 * 1024,
          "max_pieces": n, "static_contig": 1, "tabs": mem.alloc(len(tabs), data=tabs)}
@@ -1104,16 +1148,16 @@ def batch_memory(data, off, ln, tabs: bytes, expect=None, last_of=None, shards: 
 
 def accumulators(mem: Memory, f: dict):
     """The verify accumulators: (lowest posted block, final arrival word, the 8 shard arrival words)."""
-    return (mem.r64(f["vacc"]), mem.r64(f["vacc"] + 8)) + tuple(
-        mem.r64(f["vacc"] + 8 * VACC_STRIDE * (1 + s)) for s in range(VACC_SHARDS))
+    return (mem.peek64(f["vacc"]), mem.peek64(f["vacc"] + 8)) + tuple(
+        mem.peek64(f["vacc"] + 8 * VACC_STRIDE * (1 + s)) for s in range(VACC_SHARDS))
 
 
 def batch_results(mem: Memory, f: dict, published: bool = True):
     """(out words, mask of blocks written, first_bad or -1, nbad); a verify call must also leave its accumulators in
     their reset state (~0, 0) for the next call"""
     out = mem.view(f["out"], 4 * f["count"]).view(np.uint32).copy()
-    fb = mem.r64(f["first_bad"]) if "first_bad" in f else (1 << 64) - 1
-    nb = mem.r64(f["nbad"]) if "nbad" in f else 0
+    fb = mem.peek64(f["first_bad"]) if "first_bad" in f else (1 << 64) - 1
+    nb = mem.peek64(f["nbad"]) if "nbad" in f else 0
     if published and "vacc" in f and accumulators(mem, f) != ((1 << 64) - 1,) + (0,) * (1 + VACC_SHARDS):
         raise EmuError("verify accumulators not reset: %s" % [hex(x) for x in accumulators(mem, f)])
     # a written word equals the sentinel only by chance (1 in 2^32): callers compare against the oracle
@@ -1133,21 +1177,26 @@ def slots(mem: Memory, f: dict, n: int):
 
 def run_batch_kernel(asm: str, name: str, threads: int, data: np.ndarray, off, ln, tabs: bytes, wg: int = 0,
                      grid: int = 256, hint: int = 0, expect=None, lds_bytes: int = 160768, last: bool = True,
-                     state: dict | None = None, init=None, shards: int = 1, vslot: bool = False):
+                     state: dict | None = None, init=None, shards: int = 1, vslot: bool = False, wgs=None,
+                     **image):
     """Run workgroup `wg` of a batch kernel (a PiecesArgs kernel in static, unplanned mode) over the given batch.
     Verify form: with `last` the other grid - 1 workgroups count as arrived, so this one publishes the verdict; without
     it, it is an early one and `state` (a dict) receives the accumulators it leaves.  vslot: a captured call's form --
     the workgroup writes its verdict slot (state["slots"]: every slot of the grid) and touches neither the
-    accumulators nor the caller's words.
+    accumulators nor the caller's words.  wgs: the workgroups to run, one after another, in place of `wg` (the captured
+    form, or a grid of one: no arrival count depends on the others).  image: batch_memory's slack / guard / skew /
+    track; state["mem"], state["fields"] then give the image back, access marks included.
     Returns (out words, mask of blocks written, first_bad or -1, nbad, instructions executed)."""
     mem, f = batch_memory(data, off, ln, tabs, expect, last_of=(wg, grid) if last and not vslot else None,
-                          shards=shards)
+                          shards=shards, **image)
     f["hint"] = hint
     if vslot:
         alloc_slots(mem, f, grid)
     if init is not None:  # per-block initial CRCs (Extend(init[i], block i))
         f["init"] = mem.alloc(4 * len(init), data=np.asarray(init, np.uint32))
-    steps = launch(mem, asm, name, threads, lds_bytes, f, grid, [wg])
+    if state is not None:  # before the run: an EmuError leaves the image to look at
+        state["mem"], state["fields"] = mem, f
+    steps = launch(mem, asm, name, threads, lds_bytes, f, grid, [wg] if wgs is None else wgs)
     if state is not None and "vacc" in f:
         state["vacc"] = accumulators(mem, f)
     if state is not None and vslot:
@@ -1160,12 +1209,15 @@ TAB_ZSMALL = 4096 * 9 + 1024 + 4096   # z1024, z4, ztree[6], byte1, zpiece, znar
 
 
 def run_planned_batch(asm: str, pieces: str, combine: str, data: np.ndarray, off, ln, tabs: bytes, piece_k: int = 0,
-                      grid: int = 256, expect=None, state: dict | None = None):
+                      grid: int = 256, expect=None, state: dict | None = None, pieces_wgs=(5,), captured=None,
+                      **image):
     """One planned (split-block) call as launch_batch_in issues it: the piece table built on the host exactly as
     crc32c_plan_count_kernel / InclusiveSum / crc32c_plan_expand_kernel build it, the pieces kernel (dynamic
     schedule; one workgroup takes every item), then every workgroup of the combine kernel.  Pieces are
     zsmall[piece_k]'s 16 KiB << piece_k.  state (a dict, verify form): the call as captured -- verdict slots, the
-    combine kernel's after the pieces kernel's (vslot_base = grid); state["slots"] receives them all.
+    combine kernel's after the pieces kernel's (vslot_base = grid); state["slots"] receives them all.  captured:
+    whether the call is the captured form (default: whenever state is given).  pieces_wgs: the workgroups of the
+    pieces kernel to run; image: batch_memory's slack / guard / skew / track (state["mem"], state["fields"]).
     Returns (out, written, first_bad, nbad, instructions)."""
     ln = np.asarray(ln, np.uint64)
     n = ln.size
@@ -1175,20 +1227,24 @@ def run_planned_batch(asm: str, pieces: str, combine: str, data: np.ndarray, off
     pstart[1:] = np.cumsum(counts, dtype=np.uint64)
     npieces = int(pstart[-1])
     pblk = np.repeat(np.arange(n, dtype=np.uint32), counts.astype(np.int64))
-    mem, f = batch_memory(data, off, ln, tabs, expect)  # a split batch: the combine kernel's last workgroup publishes
+    captured = state is not None if captured is None else captured
+    # a split batch: the combine kernel's last workgroup publishes
+    mem, f = batch_memory(data, off, ln, tabs, expect, **image)
     f.update(pstart=mem.alloc(8 * (n + 1), data=pstart), pblk=mem.alloc(4 * npieces, data=pblk),
              partial=mem.alloc(4 * npieces), work_counter=mem.alloc(16), piece_bytes=P, max_pieces=npieces,
              zpiece=f["tabs"] + TAB_ZSMALL + 4096 * piece_k, guided_div=0, guided_cap=0)
     # one workgroup takes every item; not workgroup 0, so its shard (5) is one the combine grid below may not have:
     # the planned kernel's counts must reach the publishing grid anyway
     cgrid = min((n + 255) // 256, 2048)  # kCombineMaxGrid
-    if state is not None:
+    if captured:
         alloc_slots(mem, f, grid + cgrid)
-    steps = launch(mem, asm, pieces, 512, 160768, f, grid, [5])
     if state is not None:
+        state["mem"], state["fields"] = mem, f
+    steps = launch(mem, asm, pieces, 512, 160768, f, grid, list(pieces_wgs))
+    if captured:
         f["vslot_base"] = grid
     steps += launch(mem, asm, combine, 256, 4096, f, cgrid)
-    if state is not None:
+    if captured and state is not None:
         state["slots"] = slots(mem, f, grid + cgrid)
     return batch_results(mem, f) + (steps,)
 
