@@ -108,7 +108,8 @@ int kvsep_crc32c_ctx_set_host_node(kvsep_crc32c_ctx* ctx, int node);
 int kvsep_crc32c_ctx_host_placement(kvsep_crc32c_ctx* ctx, int* device_node, int* staging_node, int* cpus, int cap);
 /* Pre-size scratch so later calls of up to `count` blocks / `total_bytes` bytes do not allocate: the context's own
  * scratch (eager calls) and every free capture set (at least 4 are made).  Required before graph capture; covers the
- * planned, narrow, verify and SST-verify forms. */
+ * planned, narrow, verify and SST-verify forms: any batch within both numbers, whatever piece size it picks, and the SST
+ * read check called with the caller's own total_bytes. */
 int kvsep_crc32c_reserve(kvsep_crc32c_ctx* ctx, uint64_t count, uint64_t total_bytes);
 /* Graph capture (hipStreamBeginCapture ... EndCapture, torch.cuda.graph): every call captured into one graph runs on
  * that capture's own capture set -- its piece plan, work counter, SST arrays and verify verdict slots -- held by it until

@@ -43,6 +43,7 @@
 #include "gf2.h"
 #include "kvsep_testing.h"
 #include "kvsep_internal.h"
+#include "plan_size.h"
 
 namespace kvsep {
 
@@ -224,8 +225,9 @@ int ensure_sst(Scratch& sc, uint64_t count, bool capturing = false) {
   return KVSEP_OK;
 }
 
-int ensure_plan(Scratch& sc, uint64_t piece_bytes, uint64_t count, uint64_t total_bytes, bool capturing = false) {
-  const uint64_t pieces = count + total_bytes / piece_bytes + 1;
+// Room for a plan of `count` blocks and `pieces` entries (plan_size.h: pieces_needed of a call, pieces_reserved of a
+// reservation).
+int ensure_plan(Scratch& sc, uint64_t count, uint64_t pieces, bool capturing = false) {
   // hipcub's scan takes an int item count; piece and block indices are u32 in the kernels
   if (count > 0x7fffffffull) return set_err(KVSEP_EINVAL, "more than 2^31 - 1 blocks in one batch that needs a plan");
   if (pieces > 0xffffffffull) return set_err(KVSEP_EINVAL, "batch too large for u32 piece indices");
@@ -329,19 +331,35 @@ bool use_narrow(const kvsep_crc32c_ctx* c, uint64_t count, uint64_t total_bytes,
          (max_len <= kNarrowMax && count >= 128 * cus);
 }
 
-// Piece size of a planned batch.  With the default setting, a batch too small to give every wave two pieces
-// of piece_bytes gets 64, 32 or 16 KiB pieces instead: the largest size that still makes >= 2 pieces per wave
-// (64 blocks of 1 MiB: 16 KiB pieces).  Large batches keep piece_bytes.
-uint64_t piece_for(const kvsep_crc32c_ctx* c, uint64_t total_bytes, const uint32_t** zp) {
-  *zp = &c->d_tabs->zpiece[0][0];
-  if (!c->piece_auto) return c->piece_bytes;
-  const uint64_t want = 2 * uint64_t(c->num_cus) * (kWgThreads / 64);
-  uint64_t P = c->piece_bytes;
-  for (int k = 2; k >= 0 && total_bytes / P < want; --k) {
-    P = kSmallPiece << k;
-    *zp = &c->d_tabs->zsmall[k][0][0];
+static_assert(kWgThreads / 64 == kPlanWavesPerWg, "plan_size.h sizes plans for the default CRC workgroup");
+
+// What a batch call runs as: split into pieces through a plan or not, the piece size and its table (plan::piece_for:
+// smaller pieces for small batches under the default setting), and the schedule.  launch_batch_body runs what this
+// says and kvsep_crc32c_plan_query reports it.
+struct Route {
+  bool planned;
+  uint64_t piece_bytes;
+  const uint32_t* zpiece;
+  bool dyn;
+};
+
+Route route_batch(const kvsep_crc32c_ctx* c, uint64_t count, uint64_t total_bytes, uint64_t max_len) {
+  Route r;
+  r.planned = !(max_len != 0 && max_len <= c->piece_bytes);
+  r.piece_bytes = c->piece_bytes;
+  r.zpiece = &c->d_tabs->zpiece[0][0];
+  if (r.planned) {
+    const plan::Piece p = plan::piece_for(c->piece_bytes, c->piece_auto, c->num_cus, total_bytes);
+    r.piece_bytes = p.bytes;
+    if (p.table >= 0) r.zpiece = &c->d_tabs->zsmall[p.table][0][0];
   }
-  return P;
+  // auto schedule: guided (one atomic per grab) for planned batches with many pieces; static for the rest --
+  // a few thousand small pieces would spend most of the kernel in single-item grabs on one counter
+  // (~88 dequeues/us, MI355X_MICROARCH.md dequeue)
+  const uint64_t est_items = r.planned ? count + total_bytes / r.piece_bytes : count;
+  const uint64_t nwaves_est = uint64_t(c->num_cus) * (kWgThreads / 64);
+  r.dyn = c->dynamic < 0 ? (r.planned && est_items >= 8 * nwaves_est) : c->dynamic == 1;
+  return r;
 }
 
 hipEvent_t take_event(kvsep_crc32c_ctx* c) {
@@ -487,14 +505,16 @@ int launch_batch_body(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capt
                       const void* base, const uint64_t* off, const uint64_t* len, const uint32_t* init,
                       const uint32_t* expect, uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint64_t count,
                       uint64_t total_bytes, uint64_t max_len) {
-  const bool planned = !(max_len != 0 && max_len <= c->piece_bytes);
+  const Route route = route_batch(c, count, total_bytes, max_len);
+  const bool planned = route.planned;
   a.base = static_cast<const uint8_t*>(base);
   a.off = off;
   a.len = len;
   a.init = init;
   a.out = out;
   a.count = count;
-  a.piece_bytes = planned ? piece_for(c, total_bytes, &a.zpiece) : c->piece_bytes;
+  a.piece_bytes = route.piece_bytes;
+  a.zpiece = planned ? route.zpiece : nullptr;
   a.tabs = c->d_tabs;
   if (expect) {
     if (!first_bad || !nbad) {
@@ -514,12 +534,7 @@ int launch_batch_body(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capt
   // the A/B variants of the KVSEP_DIAG tools build fall back to the separate verify_finish_kernel pass.
   bool fused = true;
   if (count == 0) return KVSEP_OK;
-  // auto schedule: guided (one atomic per grab) for planned batches with many pieces; static for the rest --
-  // a few thousand small pieces would spend most of the kernel in single-item grabs on one counter
-  // (~88 dequeues/us, MI355X_MICROARCH.md dequeue)
-  const uint64_t est_items = planned ? count + total_bytes / a.piece_bytes : count;
-  const uint64_t nwaves_est = uint64_t(c->num_cus) * (kWgThreads / 64);
-  const bool dyn = c->dynamic < 0 ? (planned && est_items >= 8 * nwaves_est) : c->dynamic == 1;
+  const bool dyn = route.dyn;
   a.static_contig = c->static_contig;
   a.guided_div = 0;  // adaptive (crc32c_pieces_kernel)
   a.guided_cap = 0;
@@ -531,7 +546,7 @@ int launch_batch_body(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capt
   // The start-state words (pstart[0], the guided counter) are written by a kernel of the call, never by a memset node
   // (see crc32c_plan_count_kernel).
   if (planned) {
-    int rc = ensure_plan(sc, a.piece_bytes, count, total_bytes, capturing);
+    int rc = ensure_plan(sc, count, plan::pieces_needed(a.piece_bytes, count, total_bytes), capturing);
     if (rc) return rc;
     a.pstart = sc.d_pstart;
     a.pblk = sc.d_pblk;
@@ -760,7 +775,9 @@ int kvsep_crc32c_ctx_inject_failure(kvsep_crc32c_ctx* c) {
 }  // extern "C"
 
 namespace {
-// Everything a call of up to count blocks / total_bytes could allocate on this scratch.
+// Everything a call of up to count blocks / total_bytes could allocate on this scratch: the plan is sized for the
+// worst of the piece sizes a smaller batch can pick, and for the SST read check's extra byte per block
+// (plan::pieces_reserved).
 int reserve_scratch(kvsep_crc32c_ctx* c, Scratch& sc, uint64_t count, uint64_t total_bytes) {
   if (!sc.d_counter) KVSEP_HIP(hipMalloc(&sc.d_counter, 16));
   int rc = ensure_verify(sc);
@@ -770,8 +787,7 @@ int reserve_scratch(kvsep_crc32c_ctx* c, Scratch& sc, uint64_t count, uint64_t t
   if (rc) return rc;
   rc = ensure_vslot(sc, vslots_needed(c));
   if (rc) return rc;
-  const uint32_t* zp = nullptr;
-  return ensure_plan(sc, piece_for(c, total_bytes, &zp), count, total_bytes);
+  return ensure_plan(sc, count, plan::pieces_reserved(c->piece_bytes, c->piece_auto, c->num_cus, count, total_bytes));
 }
 
 // At least n capture sets, each free one sized for the context's largest reservation (held ones stay as their graph
@@ -948,6 +964,17 @@ const char* kvsep_crc32c_kernel_name(kvsep_crc32c_ctx* c, uint64_t count, uint64
          : nf == 10 || nf == 11 ? "crc32c_narrow_claim_kernel"
          : nf == 12             ? "crc32c_narrow_coop_kernel"
                                 : "crc32c_narrow_kernel";
+}
+
+int kvsep_crc32c_plan_query(kvsep_crc32c_ctx* c, uint64_t count, uint64_t total_bytes, uint64_t max_len,
+                            uint64_t* piece_bytes, uint64_t* pieces_needed, int* guided) {
+  if (!c) return set_err(KVSEP_EINVAL, "null ctx");
+  std::lock_guard<std::mutex> g(c->mu);
+  const Route r = route_batch(c, count, total_bytes, max_len);
+  if (piece_bytes) *piece_bytes = r.piece_bytes;
+  if (pieces_needed) *pieces_needed = r.planned ? plan::pieces_needed(r.piece_bytes, count, total_bytes) : 0;
+  if (guided) *guided = r.dyn ? 1 : 0;
+  return KVSEP_OK;
 }
 
 int kvsep_stream_read_device(kvsep_crc32c_ctx* c, void* stream, const void* src, uint64_t nbytes, uint32_t* sink) {

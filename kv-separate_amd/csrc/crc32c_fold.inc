@@ -25,7 +25,7 @@ struct DevTables {
   uint32_t xinv[16];        // x^(-8k) mod P: Z_k^-1, a register rewound over k bytes (the padded-head variant)
 };
 static_assert(sizeof(DevTables) == 4096 * 13 + 1024 + 256 + 64, "table layout");
-constexpr uint64_t kSmallPiece = 16 * 1024;  // zsmall[k] is Z_{kSmallPiece << k}
+// zsmall[k] is Z_{kSmallPiece << k} (kSmallPiece: plan_size.h)
 
 struct PiecesArgs {
   const uint8_t* base;

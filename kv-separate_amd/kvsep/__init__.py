@@ -59,6 +59,9 @@ _SIGS = {
     "kvsep_crc32c_ctx_host_placement": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                        ctypes.c_void_p, ctypes.c_int]),
     "kvsep_crc32c_ctx_inject_failure": (ctypes.c_int, [ctypes.c_void_p]),
+    "kvsep_crc32c_plan_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                               ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                               ctypes.POINTER(ctypes.c_int)]),
     "kvsep_device_pci_bus_id": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
     "kvsep_pci_numa_node": (ctypes.c_int, [ctypes.c_char_p]),
     "kvsep_device_numa_node": (ctypes.c_int, [ctypes.c_int]),
@@ -328,6 +331,14 @@ class Context:
     def kernel_name(self, count: int, max_len: int, total_bytes: int = 0) -> str:
         """The main kernel a batch of `count` blocks with these max_len / total_bytes hints runs on."""
         return lib().kvsep_crc32c_kernel_name(self._h, count, total_bytes, max_len).decode()
+
+    def plan_query(self, count: int, max_len: int, total_bytes: int = 0):
+        """(piece_bytes, pieces_needed, guided) of a batch with these hints (tests; csrc/kvsep_testing.h): the piece
+        size it is cut at, the plan entries it needs (0: unsplit, no plan) and whether it runs the guided schedule."""
+        pb, pn, gd = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int()
+        _check(lib().kvsep_crc32c_plan_query(self._h, count, total_bytes, max_len, ctypes.byref(pb), ctypes.byref(pn),
+                                             ctypes.byref(gd)), "plan_query")
+        return pb.value, pn.value, bool(gd.value)
 
     def set_timing(self, on: bool):
         _check(lib().kvsep_crc32c_ctx_set_timing(self._h, 1 if on else 0), "set_timing")

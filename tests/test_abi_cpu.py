@@ -69,6 +69,14 @@ def test_fault_injection_is_not_public_and_needs_the_test_environment():
     assert kvsep.lib().kvsep_crc32c_ctx_inject_failure(None) == -1
 
 
+def test_plan_query_is_a_test_entry_point():
+    """kvsep_crc32c_plan_query (csrc/kvsep_testing.h) is exported for the tests, bound by the package, not in the
+    public header, and refuses a null context before any device is touched."""
+    assert "kvsep_crc32c_plan_query" not in kvsep.header_functions()
+    assert "kvsep_crc32c_plan_query" in kvsep._SIGS
+    assert kvsep.lib().kvsep_crc32c_plan_query(None, 1, 1, 0, None, None, None) == -1
+
+
 def test_python_extend_rejects_n_past_buffer():
     with pytest.raises(ValueError):
         kvsep.extend(0, b"abc", 4)

@@ -121,9 +121,8 @@ def test_overlapping_verify_graphs_are_exact(oracle):
 
 @pytest.mark.parametrize("kind", ["claim", "sorted", "wide"])
 def test_one_verify_graph_replayed_over_itself(kind, oracle):
-    """One captured verify graph launched on two streams back to back, so its replays may overlap (and a second
-    instantiation of the same capture on a third): the verdict slots of its capture set are written whole by each
-    replay with the same words, so every verdict is exact."""
+    """One captured verify graph launched on two streams back to back, so its replays may overlap: the verdict slots
+    of its capture set are written whole by each replay with the same words, so every verdict is exact."""
     off, ln, hint = _layout(kind, 42)
     span = int(off[-1] + ln[-1])
     data = torch.empty(span + 64, dtype=torch.uint8, device=DEV)
