@@ -34,7 +34,9 @@ extern "C" {
  * are not counted at all); new entry points for the host legs, topology and host placement; no signature changed.
  * 4 (round 6): graph captures get capture sets of their own (kvsep_crc32c_reserve_captures / _release_captures /
  * _capture_sets); the fault-injection hook left this header (csrc/kvsep_testing.h) and works only under
- * KVSEP_TEST_HOOKS=1; no signature changed.
+ * KVSEP_TEST_HOOKS=1; no signature changed.  ABI 4 later gained the list forms of the verify calls
+ * (kvsep_crc32c_verify_list_device, kvsep_sst_verify_list_device / _host, kvsep_log_verify_device,
+ * kvsep_crc32c_group_verify_list_device): new entry points only, no signature changed, so the version stays 4.
  * The reference's C++ symbol leveldb::crc32c::Extend is not in this library: it is in the libkvsep_leveldb_abi.so
  * shim. */
 #define KVSEP_ABI_VERSION 4
@@ -108,7 +110,7 @@ int kvsep_crc32c_ctx_set_host_node(kvsep_crc32c_ctx* ctx, int node);
 int kvsep_crc32c_ctx_host_placement(kvsep_crc32c_ctx* ctx, int* device_node, int* staging_node, int* cpus, int cap);
 /* Pre-size scratch so later calls of up to `count` blocks / `total_bytes` bytes do not allocate: the context's own
  * scratch (eager calls) and every free capture set (at least 4 are made).  Required before graph capture; covers the
- * planned, narrow, verify and SST-verify forms: any batch within both numbers, whatever piece size it picks, and the SST
+ * planned, narrow, verify, list and SST-verify forms: any batch within both numbers, whatever piece size it picks, and the SST
  * read check called with the caller's own total_bytes. */
 int kvsep_crc32c_reserve(kvsep_crc32c_ctx* ctx, uint64_t count, uint64_t total_bytes);
 /* Graph capture (hipStreamBeginCapture ... EndCapture, torch.cuda.graph): every call captured into one graph runs on
@@ -150,7 +152,8 @@ const char* kvsep_crc32c_kernel_name(kvsep_crc32c_ctx* ctx, uint64_t count, uint
  * least one byte of a block of the batch (the cooperative kernel, reachable through kvsep_crc32c_ctx_set_kernel
  * only: 128-B lines that do), so never a page no block touches.  A block with len[i] == 0 is never dereferenced,
  * whatever off[i] is; out[i] = its init.  off, len, init (and expected_masked) are read for exactly `count`
- * elements, out is written for exactly `count`; the payload is never written. */
+ * elements, out is written for exactly `count`; the payload is never written.  The list forms write bad_idx for at
+ * most bad_cap elements (exactly min(*nbad, bad_cap), the rest is left as it was) and ok for exactly `count`. */
 int kvsep_crc32c_batch_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, const uint64_t* off,
                               const uint64_t* len, const uint32_t* init, uint32_t* out, uint64_t count,
                               uint64_t total_bytes, uint64_t max_len);
@@ -163,6 +166,24 @@ int kvsep_crc32c_verify_device(kvsep_crc32c_ctx* ctx, void* stream, const void* 
                                const uint64_t* len, const uint32_t* init, const uint32_t* expected_masked,
                                uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint64_t count,
                                uint64_t total_bytes, uint64_t max_len);
+
+/* List form: kvsep_crc32c_verify_device, followed on the same stream by a device pass that says WHICH blocks
+ * mismatch -- what a reader that skips exactly the bad blocks and keeps the rest needs (RepairDB::ScanTable,
+ * db/repair.cc:220-260; paranoid reads, table/format.cc:99-106), where *first_bad / *nbad serve a reader that truncates.
+ *   bad_idx[0 .. min(*nbad, bad_cap))  (device, u64) the mismatching block indices, ascending.  Nothing is written past
+ *                                      that; *nbad is the full count, so *nbad > bad_cap says the list was cut.
+ *                                      May be NULL iff bad_cap == 0.
+ *   ok[0 .. count)                     (device, u8, nullable) 1 where Mask(out[i]) == expected_masked[i], else 0; every
+ *                                      byte is written, on a clean batch too.
+ * first_bad / nbad may be NULL as in the verify form.  On a clean batch with ok == NULL the list pass costs its three
+ * launches only: each returns after loading *nbad.  Scratch (one word and one base per 1,024 blocks) is sized by
+ * kvsep_crc32c_reserve(ctx, count, ...) like the other forms', so a reserved call allocates nothing and can be
+ * captured; a captured call with more blocks than reserved fails with KVSEP_EINVAL. */
+int kvsep_crc32c_verify_list_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, const uint64_t* off,
+                                    const uint64_t* len, const uint32_t* init, const uint32_t* expected_masked,
+                                    uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint64_t* bad_idx,
+                                    uint64_t bad_cap, uint8_t* ok, uint64_t count, uint64_t total_bytes,
+                                    uint64_t max_len);
 
 /* ---------------------------------------------------------------- batched host form
  * Host pointers.  Blocks are gathered into pinned staging, copied H2D, checksummed and the
@@ -197,6 +218,13 @@ uint64_t kvsep_log_walk(const char* buf, uint64_t n, uint64_t* off, uint64_t* le
                         uint64_t cap);
 int kvsep_log_verify_host(kvsep_crc32c_ctx* ctx, const char* buf, uint64_t n, uint8_t* ok, uint64_t cap,
                           uint64_t* nrecords);
+/* Device-resident form of the checksum step of kvsep_log_verify_host: base is the log image on the device, off / len /
+ * stored the arrays kvsep_log_walk produced, copied to the device; ok[i] (device, u8, exactly `count` written) =
+ * (Value(type || payload) == Unmask(stored[i])), the verdict kvsep_log_accept consumes.  Asynchronous on `stream`;
+ * total_bytes / max_len are hints as in kvsep_crc32c_batch_device; scratch sized by kvsep_crc32c_reserve. */
+int kvsep_log_verify_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, const uint64_t* off,
+                            const uint64_t* len, const uint32_t* stored, uint8_t* ok, uint64_t count,
+                            uint64_t total_bytes, uint64_t max_len);
 /* log / MANIFEST write side (db/log_writer.cc:35-115): appends `count` records to a log of current length
  * dest_length (the writer's block_offset_ = dest_length % 32 KiB, log_writer.cc:27-28), fragmenting each record
  * over 32 KiB blocks as FULL / FIRST / MIDDLE / LAST physical records and zero-filling block trailers of
@@ -219,6 +247,14 @@ int kvsep_sst_trailers_device(kvsep_crc32c_ctx* ctx, void* stream, const void* b
 int kvsep_sst_verify_device(kvsep_crc32c_ctx* ctx, void* stream, const void* file_base, const uint64_t* off,
                             const uint64_t* len, uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint64_t count,
                             uint64_t total_bytes, uint64_t max_len);
+/* List form of the read check: as kvsep_sst_verify_device, plus bad_idx / bad_cap / ok as in
+ * kvsep_crc32c_verify_list_device -- every block ReadBlock would report as "block checksum mismatch", by index: the
+ * call for RepairDB::ScanTable (db/repair.cc:220-260) and paranoid compaction inputs, which skip those and keep the
+ * rest. */
+int kvsep_sst_verify_list_device(kvsep_crc32c_ctx* ctx, void* stream, const void* file_base, const uint64_t* off,
+                                 const uint64_t* len, uint32_t* out, uint64_t* first_bad, uint64_t* nbad,
+                                 uint64_t* bad_idx, uint64_t bad_cap, uint8_t* ok, uint64_t count, uint64_t total_bytes,
+                                 uint64_t max_len);
 /* Host-resident forms of the two above, for blocks the way TableBuilder::WriteRawBlock (table/table_builder.cc:209-232)
  * and ReadBlock (table/format.cc:73-108) hold them: in host memory.  Both go through the pinned staging pipeline of
  * the host forms; blocking.
@@ -232,6 +268,13 @@ int kvsep_sst_trailers_host(kvsep_crc32c_ctx* ctx, const char* const* block, con
                             uint32_t* masked_out, uint64_t count);
 int kvsep_sst_verify_host(kvsep_crc32c_ctx* ctx, const char* file, uint64_t n, const uint64_t* off, const uint64_t* len,
                           uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint64_t count);
+/* kvsep_sst_verify_host plus the list (host array bad_idx, at most bad_cap entries, ascending; NULL iff bad_cap == 0):
+ * the same handle checks; the image is copied to the device for the call and the list comes from the device pass of
+ * kvsep_sst_verify_list_device, not from a second compare on the host.  Blocking; KVSEP_ENOMEM if the image does not
+ * fit in device memory. */
+int kvsep_sst_verify_list_host(kvsep_crc32c_ctx* ctx, const char* file, uint64_t n, const uint64_t* off,
+                               const uint64_t* len, uint32_t* out, uint64_t* first_bad, uint64_t* nbad,
+                               uint64_t* bad_idx, uint64_t bad_cap, uint64_t count);
 
 /* ---------------------------------------------------------------- several GPUs in one process
  * Blocks are independent, so a batch is cut into contiguous block ranges balanced by bytes and each range runs on
@@ -273,6 +316,16 @@ int kvsep_crc32c_group_verify_device(kvsep_crc32c_group* g, const void* const* b
                                      const uint32_t* const* expected_masked, uint32_t* const* out,
                                      const uint64_t* index_base, const uint64_t* count, const uint64_t* total_bytes,
                                      const uint64_t* max_len, uint64_t* first_bad, uint64_t* nbad);
+
+/* ... list form: each member lists its shard's bad blocks on its device (kvsep_crc32c_verify_list_device); the host
+ * merges the shard lists into global indices index_base[i] + k, ascending, into bad_idx[0 .. min(*nbad, bad_cap))
+ * (a HOST array here, like first_bad / nbad; NULL iff bad_cap == 0).  *nbad is the total over all shards. */
+int kvsep_crc32c_group_verify_list_device(kvsep_crc32c_group* g, const void* const* base, const uint64_t* const* off,
+                                          const uint64_t* const* len, const uint32_t* const* init,
+                                          const uint32_t* const* expected_masked, uint32_t* const* out,
+                                          const uint64_t* index_base, const uint64_t* count,
+                                          const uint64_t* total_bytes, const uint64_t* max_len, uint64_t* first_bad,
+                                          uint64_t* nbad, uint64_t* bad_idx, uint64_t bad_cap);
 
 /* ---------------------------------------------------------------- topology and host placement (round 5)
  * Which physical GPU a caller runs on, and the NUMA node its host legs belong on.  sysfs is read under

@@ -24,7 +24,8 @@
 // Castagnoli polynomial (gf2.h); no table is copied from the reference.
 //
 // One translation unit, in parts: crc32c_fold.inc (the shared device code), crc32c_wide.inc (the wide kernel),
-// crc32c_narrow.inc (the narrow kernels for short blocks), crc32c_support.inc (combine, plan, helpers), then this
+// crc32c_narrow.inc (the narrow kernels for short blocks), crc32c_support.inc (combine, plan, helpers),
+// crc32c_verdicts.inc (the list pass of the verify forms), then this
 // file's host side -- the context, kernel routing, launches and the device C ABI.  crc32c_hooks.inc holds the
 // measurement hook points (empty in the shipped library), crc32c_diag.inc the KVSEP_DIAG build's A/B forms.
 #include <hip/hip_runtime.h>
@@ -51,6 +52,7 @@ namespace kvsep {
 #include "crc32c_wide.inc"     // crc32c_pieces_kernel
 #include "crc32c_narrow.inc"   // crc32c_narrow_kernel, _claim_kernel, _sorted_kernel
 #include "crc32c_support.inc"  // combine, plan, SST helpers, generator, streaming read
+#include "crc32c_verdicts.inc" // the list pass of the verify forms: bad-block index list, per-block verdict bytes
 
 }  // namespace kvsep
 
@@ -223,6 +225,60 @@ int ensure_sst(Scratch& sc, uint64_t count, bool capturing = false) {
   KVSEP_HIP(hipMalloc(&sc.d_sst_stored, count * 4));
   sc.cap_sst = count;
   return KVSEP_OK;
+}
+
+// The list forms' tile arrays (crc32c_verdicts.inc): one total and one base per kListTile blocks.
+int ensure_list(Scratch& sc, uint64_t count, bool capturing = false) {
+  const uint64_t nt = (count + kListTile - 1) / kListTile;
+  if (nt <= sc.cap_tiles) return KVSEP_OK;
+  if (capturing)
+    return set_err(KVSEP_EINVAL, "a captured list call larger than kvsep_crc32c_reserve sized its capture set for");
+  int rc = quiesce(sc);
+  if (rc) return rc;
+  hipFree(sc.d_tile_cnt);
+  hipFree(sc.d_tile_base);
+  sc.d_tile_cnt = nullptr;
+  sc.d_tile_base = nullptr;
+  sc.cap_tiles = 0;
+  KVSEP_HIP(hipMalloc(&sc.d_tile_cnt, nt * 4));
+  KVSEP_HIP(hipMalloc(&sc.d_tile_base, nt * 8));
+  sc.cap_tiles = nt;
+  return KVSEP_OK;
+}
+
+// What a list form adds to its verify call: bad_idx[0, min(nbad, bad_cap)) and / or ok[0, count).
+struct ListOut {
+  uint64_t* bad_idx;
+  uint64_t bad_cap;
+  uint8_t* ok;
+};
+
+// The list pass over the CRCs a call just wrote.  nbad: the call's verdict word, already ordered before this on the
+// stream (null: none, every kernel runs in full).  bad_cap == 0 needs no tile arrays: only ok[] is written.
+int launch_list(Scratch& sc, hipStream_t s, bool capturing, const uint32_t* out, const uint32_t* stored,
+                const uint64_t* nbad, const ListOut& l, uint64_t count) {
+  if (!count || (!l.bad_cap && !l.ok)) return KVSEP_OK;
+  const uint64_t nt = (count + kListTile - 1) / kListTile;
+  const auto* nb = reinterpret_cast<const unsigned long long*>(nbad);
+  if (l.bad_cap) {
+    int rc = ensure_list(sc, count, capturing);
+    if (rc) return rc;
+  }
+  verdict_tile_count_kernel<<<unsigned(nt), 256, 0, s>>>(out, stored, count, nb, l.ok,
+                                                         l.bad_cap ? sc.d_tile_cnt : nullptr);
+  KVSEP_HIP(hipGetLastError());
+  if (!l.bad_cap) return KVSEP_OK;
+  verdict_tile_scan_kernel<<<1, 256, 0, s>>>(sc.d_tile_cnt, sc.d_tile_base, uint32_t(nt), nb);
+  KVSEP_HIP(hipGetLastError());
+  verdict_scatter_kernel<<<unsigned(nt), 256, 0, s>>>(out, stored, count, nb, sc.d_tile_base, l.bad_idx, l.bad_cap);
+  KVSEP_HIP(hipGetLastError());
+  return KVSEP_OK;
+}
+
+// Where a verify call put its count: the caller's word, or the scratch's own when the caller passed none
+// (launch_batch_body).
+const uint64_t* verdict_nbad(const Scratch& sc, const uint64_t* first_bad, const uint64_t* nbad) {
+  return first_bad && nbad ? nbad : reinterpret_cast<const uint64_t*>(sc.d_verify + 1);
 }
 
 // Room for a plan of `count` blocks and `pieces` entries (plan_size.h: pieces_needed of a call, pieces_reserved of a
@@ -444,7 +500,8 @@ int stream_scratch(kvsep_crc32c_ctx* c, hipStream_t s, Scratch& eager, bool* cap
 // Every use of a Scratch is bracketed by acquire/release (event ordering across streams).
 int launch_batch(kvsep_crc32c_ctx* c, Scratch& eager, hipStream_t s, const void* base, const uint64_t* off,
                  const uint64_t* len, const uint32_t* init, const uint32_t* expect, uint32_t* out, uint64_t* first_bad,
-                 uint64_t* nbad, uint64_t count, uint64_t total_bytes, uint64_t max_len) {
+                 uint64_t* nbad, uint64_t count, uint64_t total_bytes, uint64_t max_len,
+                 const ListOut* list = nullptr) {
   if (!base || !off || !len || !out) return set_err(KVSEP_EINVAL, "null pointer argument");
   // block indices travel as u32 through the descriptor windows and the piece table
   if (count > 0xffffffffull) return set_err(KVSEP_EINVAL, "more than 2^32 - 1 blocks in one batch");
@@ -461,8 +518,13 @@ int launch_batch(kvsep_crc32c_ctx* c, Scratch& eager, hipStream_t s, const void*
   Scratch& sc = *psc;
   rc = capturing ? KVSEP_OK : acquire(sc, s);
   if (rc) return rc;
+  if (list && list->bad_cap) {  // refused before anything is enqueued
+    rc = ensure_list(sc, count, capturing);
+    if (rc) return rc;
+  }
   rc = launch_batch_in(c, sc, s, capturing, base, off, len, init, expect, out, first_bad, nbad, count, total_bytes,
                        max_len);
+  if (!rc && list) rc = launch_list(sc, s, capturing, out, expect, verdict_nbad(sc, first_bad, nbad), *list, count);
   if (rc) {
     if (!capturing) (void)release(sc, s);  // whatever was enqueued stays ordered before the scratch's next user
     return rc;
@@ -662,6 +724,8 @@ void free_scratch(Scratch& sc) {
   hipFree(sc.d_vslot);
   hipFree(sc.d_sst_len1);
   hipFree(sc.d_sst_stored);
+  hipFree(sc.d_tile_cnt);
+  hipFree(sc.d_tile_base);
   if (sc.last_use) (void)hipEventDestroy(sc.last_use);
   sc = Scratch();
 }
@@ -787,6 +851,8 @@ int reserve_scratch(kvsep_crc32c_ctx* c, Scratch& sc, uint64_t count, uint64_t t
   if (rc) return rc;
   rc = ensure_vslot(sc, vslots_needed(c));
   if (rc) return rc;
+  rc = ensure_list(sc, count);
+  if (rc) return rc;
   return ensure_plan(sc, count, plan::pieces_reserved(c->piece_bytes, c->piece_auto, c->num_cus, count, total_bytes));
 }
 
@@ -888,6 +954,50 @@ int kvsep_crc32c_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* ba
                       first_bad, nbad, count, total_bytes, max_len);
 }
 
+int kvsep_crc32c_verify_list_device(kvsep_crc32c_ctx* c, void* stream, const void* base, const uint64_t* off,
+                                    const uint64_t* len, const uint32_t* init, const uint32_t* expected_masked,
+                                    uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint64_t* bad_idx,
+                                    uint64_t bad_cap, uint8_t* ok, uint64_t count, uint64_t total_bytes,
+                                    uint64_t max_len) {
+  if (!c || !expected_masked) return set_err(KVSEP_EINVAL, "kvsep_crc32c_verify_list_device: null ctx or expected_masked");
+  if (!bad_idx && bad_cap) return set_err(KVSEP_EINVAL, "kvsep_crc32c_verify_list_device: null bad_idx with bad_cap > 0");
+  std::lock_guard<std::mutex> g(c->mu);
+  const ListOut l{bad_idx, bad_cap, ok};
+  return launch_batch(c, c->sc, static_cast<hipStream_t>(stream), base, off, len, init, expected_masked, out,
+                      first_bad, nbad, count, total_bytes, max_len, &l);
+}
+
+int kvsep_log_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* base, const uint64_t* off,
+                            const uint64_t* len, const uint32_t* stored, uint8_t* ok, uint64_t count,
+                            uint64_t total_bytes, uint64_t max_len) {
+  if (!c) return set_err(KVSEP_EINVAL, "kvsep_log_verify_device: null ctx");
+  if (!base || !off || !len || !stored || !ok) return set_err(KVSEP_EINVAL, "kvsep_log_verify_device: null argument");
+  if (count > 0xffffffffull) return set_err(KVSEP_EINVAL, "kvsep_log_verify_device: more than 2^32 - 1 records");
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard dg(c->device);
+  KVSEP_HIP(dg.err);
+  bool capturing = false;
+  Scratch* psc = nullptr;
+  int rc = stream_scratch(c, s, c->sc, &capturing, &psc);
+  if (rc) return rc;
+  Scratch& sc = *psc;
+  rc = capturing ? KVSEP_OK : acquire(sc, s);
+  if (rc) return rc;
+  // the CRCs go to the scratch's u32 word per block (the SST read check's array: kvsep_crc32c_reserve sizes it), then
+  // ok[i] = Mask(crc) == stored[i], which is db/log_reader.cc:250-258's crc == Unmask(stored)
+  rc = ensure_sst(sc, count, capturing);
+  if (!rc)
+    rc = launch_batch_in(c, sc, s, capturing, base, off, len, nullptr, nullptr, sc.d_sst_stored, nullptr, nullptr,
+                         count, total_bytes, max_len);
+  if (!rc) rc = launch_list(sc, s, capturing, sc.d_sst_stored, stored, nullptr, ListOut{nullptr, 0, ok}, count);
+  if (rc) {
+    if (!capturing) (void)release(sc, s);
+    return rc;
+  }
+  return capturing ? KVSEP_OK : release(sc, s);
+}
+
 int kvsep_fill_splitmix64_device(void* stream, void* dst, uint64_t nbytes, uint64_t seed, uint64_t stream_offset) {
   if (!dst && nbytes) return set_err(KVSEP_EINVAL, "null dst");
   if (!nbytes) return KVSEP_OK;
@@ -922,10 +1032,13 @@ int kvsep_sst_trailers_device(kvsep_crc32c_ctx* c, void* stream, const void* bas
   return KVSEP_OK;
 }
 
-int kvsep_sst_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, const uint64_t* off,
-                            const uint64_t* len, uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint64_t count,
-                            uint64_t total_bytes, uint64_t max_len) {
-  if (!c || !file_base || !off || !len || !out) return set_err(KVSEP_EINVAL, "null argument");
+}  // extern "C"
+
+namespace {
+// The SST read check, and its list form when `list` is given (the stored words are the ones the prep kernel extracts).
+int sst_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, const uint64_t* off,
+                      const uint64_t* len, uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint64_t count,
+                      uint64_t total_bytes, uint64_t max_len, const ListOut* list) {
   std::lock_guard<std::mutex> g(c->mu);
   hipStream_t s = static_cast<hipStream_t>(stream);
   DeviceGuard dg(c->device);
@@ -941,6 +1054,10 @@ int kvsep_sst_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* file_
   if (rc) return rc;
   rc = ensure_sst(sc, count, capturing);
   if (rc) return rc;
+  if (list && list->bad_cap) {
+    rc = ensure_list(sc, count, capturing);
+    if (rc) return rc;
+  }
   if (count) {
     sst_verify_prep_kernel<<<unsigned((count + 255) / 256), 256, 0, s>>>(static_cast<const uint8_t*>(file_base), off,
                                                                         len, sc.d_sst_len1, sc.d_sst_stored, count);
@@ -948,11 +1065,89 @@ int kvsep_sst_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* file_
   }
   rc = launch_batch_in(c, sc, s, capturing, file_base, off, sc.d_sst_len1, nullptr, sc.d_sst_stored, out, first_bad,
                        nbad, count, total_bytes + count, max_len ? max_len + 1 : 0);
+  if (!rc && list)
+    rc = launch_list(sc, s, capturing, out, sc.d_sst_stored, verdict_nbad(sc, first_bad, nbad), *list, count);
   if (rc) {
     if (!capturing) (void)release(sc, s);
     return rc;
   }
   return capturing ? KVSEP_OK : release(sc, s);
+}
+}  // namespace
+
+extern "C" {
+
+int kvsep_sst_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, const uint64_t* off,
+                            const uint64_t* len, uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint64_t count,
+                            uint64_t total_bytes, uint64_t max_len) {
+  if (!c || !file_base || !off || !len || !out) return set_err(KVSEP_EINVAL, "null argument");
+  return sst_verify_device(c, stream, file_base, off, len, out, first_bad, nbad, count, total_bytes, max_len, nullptr);
+}
+
+int kvsep_sst_verify_list_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, const uint64_t* off,
+                                 const uint64_t* len, uint32_t* out, uint64_t* first_bad, uint64_t* nbad,
+                                 uint64_t* bad_idx, uint64_t bad_cap, uint8_t* ok, uint64_t count, uint64_t total_bytes,
+                                 uint64_t max_len) {
+  if (!c) return set_err(KVSEP_EINVAL, "kvsep_sst_verify_list_device: null ctx");
+  if (!bad_idx && bad_cap) return set_err(KVSEP_EINVAL, "kvsep_sst_verify_list_device: null bad_idx with bad_cap > 0");
+  if (!file_base || !off || !len || !out) return set_err(KVSEP_EINVAL, "kvsep_sst_verify_list_device: null argument");
+  const ListOut l{bad_idx, bad_cap, ok};
+  return sst_verify_device(c, stream, file_base, off, len, out, first_bad, nbad, count, total_bytes, max_len, &l);
+}
+
+// The host-resident list form: the image and its handles go to the device for the call (blocking), the read check and
+// its list pass run there, and the CRCs, the verdict and the list come back.
+int kvsep_sst_verify_list_host(kvsep_crc32c_ctx* c, const char* file, uint64_t n, const uint64_t* off,
+                               const uint64_t* len, uint32_t* out, uint64_t* first_bad, uint64_t* nbad,
+                               uint64_t* bad_idx, uint64_t bad_cap, uint64_t count) {
+  if (!c) return set_err(KVSEP_EINVAL, "kvsep_sst_verify_list_host: null ctx");
+  if (!bad_idx && bad_cap) return set_err(KVSEP_EINVAL, "kvsep_sst_verify_list_host: null bad_idx with bad_cap > 0");
+  if ((!file && n) || (count && (!off || !len || !out)))
+    return set_err(KVSEP_EINVAL, "kvsep_sst_verify_list_host: null argument");
+  uint64_t total = 0, max_len = 0;
+  for (uint64_t i = 0; i < count; ++i) {
+    // the handle must leave room for the 5-byte trailer (table/format.cc:84-87: "truncated block read")
+    if (off[i] > n || len[i] > n - off[i] || n - off[i] - len[i] < 5)
+      return set_err(KVSEP_EINVAL,
+                     "kvsep_sst_verify_list_host: block handle (plus its 5-byte trailer) outside the file image");
+    total += len[i];
+    max_len = std::max(max_len, len[i]);
+  }
+  if (first_bad) *first_bad = ~0ull;
+  if (nbad) *nbad = 0;
+  if (!count) return KVSEP_OK;
+  const uint64_t cap = std::min(bad_cap, count);
+  struct Bufs {  // freed on every path
+    void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~Bufs() { for (void* q : p) hipFree(q); }
+  } b;
+  {
+    DeviceGuard dg(c->device);
+    KVSEP_HIP(dg.err);
+    const size_t bytes[5] = {size_t(n), size_t(count * 16), size_t(count * 4), 16, size_t(std::max<uint64_t>(cap, 1) * 8)};
+    for (int i = 0; i < 5; ++i)
+      if (hipMalloc(&b.p[i], bytes[i]) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(KVSEP_ENOMEM, "kvsep_sst_verify_list_host: device allocation failed");
+      }
+    auto* d_off = static_cast<uint64_t*>(b.p[1]);
+    auto* d_res = static_cast<uint64_t*>(b.p[3]);
+    KVSEP_HIP(hipMemcpy(b.p[0], file, n, hipMemcpyHostToDevice));
+    KVSEP_HIP(hipMemcpy(d_off, off, count * 8, hipMemcpyHostToDevice));
+    KVSEP_HIP(hipMemcpy(d_off + count, len, count * 8, hipMemcpyHostToDevice));
+    const int rc = kvsep_sst_verify_list_device(c, nullptr, b.p[0], d_off, d_off + count, static_cast<uint32_t*>(b.p[2]),
+                                                d_res, d_res + 1, cap ? static_cast<uint64_t*>(b.p[4]) : nullptr, cap,
+                                                nullptr, count, total, max_len);
+    if (rc) return rc;
+    uint64_t res[2];
+    KVSEP_HIP(hipMemcpy(res, d_res, 16, hipMemcpyDeviceToHost));  // (the null stream: after the kernels)
+    KVSEP_HIP(hipMemcpy(out, b.p[2], count * 4, hipMemcpyDeviceToHost));
+    const uint64_t k = std::min(res[1], cap);
+    if (k) KVSEP_HIP(hipMemcpy(bad_idx, b.p[4], k * 8, hipMemcpyDeviceToHost));
+    if (first_bad) *first_bad = res[0];
+    if (nbad) *nbad = res[1];
+  }
+  return KVSEP_OK;
 }
 
 const char* kvsep_crc32c_kernel_name(kvsep_crc32c_ctx* c, uint64_t count, uint64_t total_bytes, uint64_t max_len) {

@@ -25,7 +25,9 @@ struct kvsep_crc32c_group {
   std::vector<kvsep_crc32c_ctx*> ctx;
   std::vector<hipStream_t> stream;  // device-resident form: one stream per member, on its device
   std::vector<uint64_t*> d_res;      // verify form: [first_bad, nbad] of each member's shard, on its device
-  std::mutex mu;                     // device-resident calls share the streams and d_res: one at a time
+  std::vector<uint64_t*> d_list;     // list form: each member's shard list, on its device (grown on demand)
+  std::vector<uint64_t> list_cap;
+  std::mutex mu;                     // device-resident calls share the streams, d_res and d_list: one at a time
   // each member's host node and its CPU list, read from sysfs once per node (not on every call)
   std::mutex node_mu;
   std::vector<int> node;
@@ -134,6 +136,8 @@ int kvsep_crc32c_group_create(const int* devices, int ndev, kvsep_crc32c_group**
     g->ctx.push_back(c);
     g->stream.push_back(s);
     g->d_res.push_back(res);
+    g->d_list.push_back(nullptr);
+    g->list_cap.push_back(0);
     g->node.push_back(-2);  // not read yet (member_cpus)
     g->node_cpus.emplace_back();
   }
@@ -149,6 +153,7 @@ void kvsep_crc32c_group_destroy(kvsep_crc32c_group* g) {
       (void)hipStreamSynchronize(g->stream[i]);
       (void)hipStreamDestroy(g->stream[i]);
       (void)hipFree(g->d_res[i]);
+      (void)hipFree(g->d_list[i]);
     }
     kvsep_crc32c_ctx_destroy(g->ctx[i]);
   }
@@ -231,11 +236,16 @@ int kvsep_crc32c_group_batch_device(kvsep_crc32c_group* g, const void* const* ba
                                           nullptr, nullptr);
 }
 
-int kvsep_crc32c_group_verify_device(kvsep_crc32c_group* g, const void* const* base, const uint64_t* const* off,
-                                     const uint64_t* const* len, const uint32_t* const* init,
-                                     const uint32_t* const* expected_masked, uint32_t* const* out,
-                                     const uint64_t* index_base, const uint64_t* count, const uint64_t* total_bytes,
-                                     const uint64_t* max_len, uint64_t* first_bad, uint64_t* nbad) {
+}  // extern "C"
+
+namespace {
+// The device-resident group forms.  bad_idx (host, nullable with bad_cap 0): the list form -- every member lists up to
+// bad_cap of its shard's bad blocks on its device, and the shard lists are merged here into global indices.
+int group_verify_device(kvsep_crc32c_group* g, const void* const* base, const uint64_t* const* off,
+                        const uint64_t* const* len, const uint32_t* const* init,
+                        const uint32_t* const* expected_masked, uint32_t* const* out, const uint64_t* index_base,
+                        const uint64_t* count, const uint64_t* total_bytes, const uint64_t* max_len,
+                        uint64_t* first_bad, uint64_t* nbad, uint64_t* bad_idx, uint64_t bad_cap) {
   if (!g || !base || !off || !len || !out || !count || !total_bytes || !max_len ||
       (expected_masked && (!index_base || !first_bad || !nbad))) {
     kvsep::set_last_error("group_batch_device: bad argument");
@@ -244,6 +254,7 @@ int kvsep_crc32c_group_verify_device(kvsep_crc32c_group* g, const void* const* b
   std::lock_guard<std::mutex> lk(g->mu);
   const int n = int(g->ctx.size());
   std::vector<uint64_t> fb(n, UINT64_MAX), nb(n, 0);
+  std::vector<std::vector<uint64_t>> lists(n);
   const int rc = fan_out(g, false, [&](int i) {
     if (!count[i]) return int(KVSEP_OK);
     kvsep::DeviceGuard dg(g->devices[i]);
@@ -253,7 +264,22 @@ int kvsep_crc32c_group_verify_device(kvsep_crc32c_group* g, const void* const* b
     }
     int r;
     uint64_t* d_res = expected_masked ? g->d_res[i] : nullptr;  // [first_bad, nbad] of this shard
-    if (expected_masked) {
+    const uint64_t cap = std::min(bad_cap, count[i]);  // what this shard can add to the first bad_cap of all
+    if (cap > g->list_cap[i]) {
+      (void)hipFree(g->d_list[i]);
+      g->d_list[i] = nullptr;
+      g->list_cap[i] = 0;
+      if (hipMalloc(&g->d_list[i], cap * 8) != hipSuccess) {
+        kvsep::set_last_error("group_verify_list_device: hipMalloc failed");
+        return int(KVSEP_ENOMEM);
+      }
+      g->list_cap[i] = cap;
+    }
+    if (cap) {
+      r = kvsep_crc32c_verify_list_device(g->ctx[i], g->stream[i], base[i], off[i], len[i], init ? init[i] : nullptr,
+                                          expected_masked[i], out[i], d_res, d_res + 1, g->d_list[i], cap, nullptr,
+                                          count[i], total_bytes[i], max_len[i]);
+    } else if (expected_masked) {
       r = kvsep_crc32c_verify_device(g->ctx[i], g->stream[i], base[i], off[i], len[i], init ? init[i] : nullptr,
                                      expected_masked[i], out[i], d_res, d_res + 1, count[i], total_bytes[i], max_len[i]);
     } else {
@@ -273,11 +299,26 @@ int kvsep_crc32c_group_verify_device(kvsep_crc32c_group* g, const void* const* b
       } else {
         fb[i] = h[0] == UINT64_MAX ? UINT64_MAX : index_base[i] + h[0];
         nb[i] = h[1];
+        lists[i].resize(std::min(h[1], cap));
+        if (!lists[i].empty() &&
+            (hipMemcpyAsync(lists[i].data(), g->d_list[i], lists[i].size() * 8, hipMemcpyDeviceToHost,
+                            g->stream[i]) != hipSuccess ||
+             hipStreamSynchronize(g->stream[i]) != hipSuccess)) {
+          kvsep::set_last_error("hipMemcpy failed");
+          r = KVSEP_EHIP;
+        }
+        for (uint64_t& k : lists[i]) k += index_base[i];
       }
     }
     return r;
   });
   if (rc) return rc;
+  if (bad_cap) {  // every shard's list is ascending; the shards' index ranges may come in any order
+    std::vector<uint64_t> all;
+    for (const auto& l : lists) all.insert(all.end(), l.begin(), l.end());
+    std::sort(all.begin(), all.end());
+    std::copy(all.begin(), all.begin() + std::min<uint64_t>(all.size(), bad_cap), bad_idx);
+  }
   if (expected_masked) {
     *first_bad = *std::min_element(fb.begin(), fb.end());
     uint64_t s = 0;
@@ -285,6 +326,34 @@ int kvsep_crc32c_group_verify_device(kvsep_crc32c_group* g, const void* const* b
     *nbad = s;
   }
   return KVSEP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int kvsep_crc32c_group_verify_device(kvsep_crc32c_group* g, const void* const* base, const uint64_t* const* off,
+                                     const uint64_t* const* len, const uint32_t* const* init,
+                                     const uint32_t* const* expected_masked, uint32_t* const* out,
+                                     const uint64_t* index_base, const uint64_t* count, const uint64_t* total_bytes,
+                                     const uint64_t* max_len, uint64_t* first_bad, uint64_t* nbad) {
+  return group_verify_device(g, base, off, len, init, expected_masked, out, index_base, count, total_bytes, max_len,
+                             first_bad, nbad, nullptr, 0);
+}
+
+int kvsep_crc32c_group_verify_list_device(kvsep_crc32c_group* g, const void* const* base, const uint64_t* const* off,
+                                          const uint64_t* const* len, const uint32_t* const* init,
+                                          const uint32_t* const* expected_masked, uint32_t* const* out,
+                                          const uint64_t* index_base, const uint64_t* count,
+                                          const uint64_t* total_bytes, const uint64_t* max_len, uint64_t* first_bad,
+                                          uint64_t* nbad, uint64_t* bad_idx, uint64_t bad_cap) {
+  if (!g || !expected_masked || (!bad_idx && bad_cap)) {
+    kvsep::set_last_error(!g ? "kvsep_crc32c_group_verify_list_device: null group"
+                          : !expected_masked ? "kvsep_crc32c_group_verify_list_device: expected_masked is null"
+                                             : "kvsep_crc32c_group_verify_list_device: null bad_idx with bad_cap > 0");
+    return KVSEP_EINVAL;
+  }
+  return group_verify_device(g, base, off, len, init, expected_masked, out, index_base, count, total_bytes, max_len,
+                             first_bad, nbad, bad_idx, bad_cap);
 }
 
 }  // extern "C"

@@ -34,6 +34,9 @@ struct Scratch {
   uint64_t* d_sst_len1 = nullptr;           // SST verify: len + 1 ...
   uint32_t* d_sst_stored = nullptr;         // ... and the stored trailer words
   uint64_t cap_sst = 0;
+  uint32_t* d_tile_cnt = nullptr;            // list forms: bad blocks per tile of the batch ...
+  unsigned long long* d_tile_base = nullptr;  // ... and their exclusive prefix sum (crc32c_verdicts.inc)
+  uint64_t cap_tiles = 0;
   hipEvent_t last_use = nullptr;
   hipStream_t last_stream = nullptr;
   bool used = false;

@@ -87,6 +87,15 @@ _SIGS = {
                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
                                                   ctypes.c_uint64]),
+    "kvsep_crc32c_verify_list_device": (ctypes.c_int, [ctypes.c_void_p] * 11 + [ctypes.c_uint64, ctypes.c_void_p,
+                                                       ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64]),
+    "kvsep_sst_verify_list_device": (ctypes.c_int, [ctypes.c_void_p] * 9 + [ctypes.c_uint64, ctypes.c_void_p,
+                                                    ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64]),
+    "kvsep_sst_verify_list_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64] +
+                                   [ctypes.c_void_p] * 6 + [ctypes.c_uint64, ctypes.c_uint64]),
+    "kvsep_log_verify_device": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_uint64, ctypes.c_uint64,
+                                               ctypes.c_uint64]),
+    "kvsep_crc32c_group_verify_list_device": (ctypes.c_int, [ctypes.c_void_p] * 14 + [ctypes.c_uint64]),
     "kvsep_crc32c_batch_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_uint64]),
     "kvsep_crc32c_batch_host_span": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
@@ -370,6 +379,34 @@ class Context:
                "kvsep_crc32c_verify_device")
         return out
 
+    def verify_list_device(self, base, off, length, expected_masked, out, first_bad, nbad, bad_idx=None, bad_cap=None,
+                           ok=None, init=None, count=None, total_bytes=None, max_len=0, stream=None):
+        """verify_device, then the list pass (kvsep_crc32c_verify_list_device): bad_idx (int64 / uint64 device tensor,
+        bad_cap defaults to its length) receives the mismatching block indices, ascending, at most bad_cap of them; ok
+        (uint8 device tensor of `count`, optional) 1 / 0 per block."""
+        count = int(off.numel()) if count is None else count
+        if total_bytes is None:
+            total_bytes = int(length.sum().item()) if count else 0
+        if bad_cap is None:
+            bad_cap = 0 if bad_idx is None else int(bad_idx.numel())
+        _check(lib().kvsep_crc32c_verify_list_device(self._h, _stream_handle(stream), _dptr(base), _dptr(off),
+                                                     _dptr(length), _dptr(init), _dptr(expected_masked), _dptr(out),
+                                                     _dptr(first_bad), _dptr(nbad), _dptr(bad_idx), bad_cap, _dptr(ok),
+                                                     count, total_bytes, max_len),
+               "kvsep_crc32c_verify_list_device")
+        return out
+
+    def log_verify_device(self, base, off, length, stored, ok, count=None, total_bytes=None, max_len=0, stream=None):
+        """db/log_reader.cc:246-259 for a device-resident log image: off / length / stored as log_walk gives them, on
+        the device; ok (uint8 device tensor) = 1 where the record's checksum matches (kvsep_log_verify_device)."""
+        count = int(off.numel()) if count is None else count
+        if total_bytes is None:
+            total_bytes = int(length.sum().item()) if count else 0
+        _check(lib().kvsep_log_verify_device(self._h, _stream_handle(stream), _dptr(base), _dptr(off), _dptr(length),
+                                             _dptr(stored), _dptr(ok), count, total_bytes, max_len),
+               "kvsep_log_verify_device")
+        return ok
+
     def stream_read(self, src, nbytes: int, sink, stream=None):
         _check(lib().kvsep_stream_read_device(self._h, _stream_handle(stream), _dptr(src), nbytes, _dptr(sink)),
                "kvsep_stream_read_device")
@@ -493,6 +530,41 @@ class Context:
         _check(lib().kvsep_sst_verify_device(self._h, _stream_handle(stream), _dptr(file_base), _dptr(off),
                                              _dptr(length), _dptr(out), _dptr(first_bad), _dptr(nbad), count,
                                              total_bytes, max_len), "kvsep_sst_verify_device")
+
+    def sst_verify_list_device(self, file_base, off, length, out, first_bad, nbad, bad_idx=None, bad_cap=None, ok=None,
+                               count=None, total_bytes=None, max_len=0, stream=None):
+        """sst_verify_device, then the list pass (kvsep_sst_verify_list_device): the call for RepairDB::ScanTable and
+        paranoid reads.  bad_idx / bad_cap / ok as in verify_list_device."""
+        count = int(off.numel()) if count is None else count
+        if total_bytes is None:
+            total_bytes = int(length.sum().item()) if count else 0
+        if bad_cap is None:
+            bad_cap = 0 if bad_idx is None else int(bad_idx.numel())
+        _check(lib().kvsep_sst_verify_list_device(self._h, _stream_handle(stream), _dptr(file_base), _dptr(off),
+                                                  _dptr(length), _dptr(out), _dptr(first_bad), _dptr(nbad),
+                                                  _dptr(bad_idx), bad_cap, _dptr(ok), count, total_bytes, max_len),
+               "kvsep_sst_verify_list_device")
+
+    def sst_verify_list(self, image, off, length, bad_cap=None):
+        """sst_verify plus the bad blocks' indices (kvsep_sst_verify_list_host) -> (out, first_bad, nbad, bad): bad =
+        the first min(nbad, bad_cap) mismatching handles, ascending (bad_cap defaults to every handle)."""
+        p, keep = _buf(image)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        length = np.ascontiguousarray(length, dtype=np.uint64)
+        if off.size != length.size:
+            raise ValueError("off and length must have the same length")
+        k = off.size
+        bad_cap = k if bad_cap is None else int(bad_cap)
+        out = np.zeros(max(k, 1), dtype=np.uint32)
+        bad = np.zeros(max(bad_cap, 1), dtype=np.uint64)
+        fb, nb = ctypes.c_uint64(), ctypes.c_uint64()
+        vp = ctypes.c_void_p
+        _check(lib().kvsep_sst_verify_list_host(self._h, p, keep.nbytes, off.ctypes.data_as(vp),
+                                                length.ctypes.data_as(vp), out.ctypes.data_as(vp), ctypes.byref(fb),
+                                                ctypes.byref(nb), bad.ctypes.data_as(vp) if bad_cap else None, bad_cap,
+                                                k), "kvsep_sst_verify_list_host")
+        first = -1 if fb.value == 0xFFFFFFFFFFFFFFFF else fb.value
+        return out[:k], first, nb.value, bad[:min(nb.value, bad_cap)]
 
     def sst_trailers(self, blocks, types):
         """table/table_builder.cc:209-232 for host-resident blocks -> uint32 trailer words
@@ -671,6 +743,30 @@ class Group:
                                                       ctypes.byref(fb), ctypes.byref(nb)),
                "kvsep_crc32c_group_verify_device")
         return fb.value, nb.value
+
+    def verify_list_device(self, shards, expected_masked, index_base, bad_cap):
+        """batch_device's verify form plus the merged list (kvsep_crc32c_group_verify_list_device) -> (first_bad, nbad,
+        bad): bad = the first min(nbad, bad_cap) mismatching global indices index_base[i] + k, ascending."""
+        n = len(shards)
+        P = ctypes.c_void_p * n
+        U = ctypes.c_uint64 * n
+        base = P(*[_dptr(s["base"]).value for s in shards])
+        off = P(*[_dptr(s["off"]).value for s in shards])
+        ln = P(*[_dptr(s["len"]).value for s in shards])
+        out = P(*[_dptr(s["out"]).value for s in shards])
+        init = P(*[_dptr(s.get("init")).value for s in shards])
+        cnt = U(*[int(s["off"].numel()) for s in shards])
+        tot = U(*[int(s["total_bytes"]) for s in shards])
+        ml = U(*[int(s.get("max_len", 0)) for s in shards])
+        ex = P(*[_dptr(e).value for e in expected_masked])
+        ib = U(*[int(x) for x in index_base])
+        bad = np.zeros(max(int(bad_cap), 1), dtype=np.uint64)
+        fb, nb = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().kvsep_crc32c_group_verify_list_device(
+            self._h, base, off, ln, init, ex, out, ib, cnt, tot, ml, ctypes.byref(fb), ctypes.byref(nb),
+            bad.ctypes.data_as(ctypes.c_void_p) if bad_cap else None, int(bad_cap)),
+            "kvsep_crc32c_group_verify_list_device")
+        return fb.value, nb.value, bad[:min(nb.value, int(bad_cap))]
 
 
 def fill_splitmix64(dst, nbytes: int, seed: int, stream_offset: int = 0, stream=None):
