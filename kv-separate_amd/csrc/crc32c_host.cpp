@@ -23,6 +23,7 @@
 
 #include "../../include/kvsep_crc32c.h"
 #include "host_crc.h"
+#include "host_slots.h"
 #include "kvsep_internal.h"
 #include "numa.h"
 
@@ -57,8 +58,7 @@ std::atomic<uint64_t> g_offload_threshold{64ull << 20};
 std::atomic<uint64_t> g_gpu_calls{0}, g_host_calls{0}, g_gpu_failures{0};
 
 // ------------------------------------------------------------------ staging pipeline
-constexpr uint64_t kSlotBytes = 64ull << 20;
-constexpr uint64_t kSlotBlocks = 1ull << 16;
+// (two slots of kSlotBytes and kSlotBlocks each; how a call is cut into slot jobs: host_slots.h)
 
 int hip_fail(const char* what, hipError_t e) {
   char buf[384];
@@ -180,8 +180,9 @@ int big_block(kvsep_crc32c_ctx* c, HostStaging& s, SlotJob* jobs, uint32_t* out,
   uint32_t crc = init;
   int slot = 0;
   // Segments run on one stream; host data of segment k+1 is staged while segment k computes.
-  for (uint64_t done = 0; done < n; done += s.bytes, slot ^= 1) {
-    const uint64_t seg = std::min<uint64_t>(s.bytes, n - done);
+  const uint64_t nseg = slots::segment_count(n, s.bytes);
+  for (uint64_t k = 0; k < nseg; ++k, slot ^= 1) {
+    const uint64_t done = slots::segment(n, k, s.bytes).at, seg = slots::segment(n, k, s.bytes).bytes;
     KVSEP_HIPH(hipEventSynchronize(s.done[slot]));  // previous use of this slot's buffers finished
     if (!pinned) {
       const CopySeg cs{s.h_data[slot], p + done, seg};
@@ -273,7 +274,7 @@ int batch_host_tee(kvsep_crc32c_ctx* c, const uint32_t* init, const char* const*
   int slot = 0;
   uint64_t i = 0;
   while (i < count) {
-    if (len[i] > s.bytes) {
+    if (slots::is_long(len[i], s.bytes)) {
       uint32_t r = 0;
       rc = big_block(c, s, jobs, out, reinterpret_cast<const uint8_t*>(ptr[i]), len[i], init ? init[i] : 0u,
                      is_pinned(ptr[i]), &r);
@@ -288,24 +289,20 @@ int batch_host_tee(kvsep_crc32c_ctx* c, const uint32_t* init, const char* const*
     }
     rc = retire(s, slot, jobs[slot], out);
     if (rc) return rc;
-    uint64_t used = 0, j = i, max_len = 0;
-    // gather: blocks packed back to back, each at a 16-B aligned staging offset (copied by the pool below)
+    // gather: blocks packed back to back, each at a 16-B aligned staging offset (copied by the pool below); the
+    // offsets go straight into the slot's descriptor
+    const slots::GatherGroup g = slots::gather_group(len, i, count, s.bytes, s.max_blocks, s.h_desc[slot]);
+    const uint64_t j = g.j;
     std::vector<CopySeg> segs;
-    while (j < count && j - i < s.max_blocks && len[j] <= s.bytes) {
-      const uint64_t at = (used + 15) & ~uint64_t(15);
-      if (at + len[j] > s.bytes) break;
-      if (len[j])
-        segs.push_back({s.h_data[slot] + at, reinterpret_cast<const uint8_t*>(ptr[j]), len[j],
-                        tee ? reinterpret_cast<uint8_t*>(tee[j]) : nullptr});
-      s.h_desc[slot][j - i] = at;
-      s.h_desc[slot][s.max_blocks + (j - i)] = len[j];
-      if (init) s.h_init[slot][j - i] = init[j];
-      max_len = std::max(max_len, len[j]);
-      used = at + len[j];
-      ++j;
+    for (uint64_t k = i; k < j; ++k) {
+      if (len[k])
+        segs.push_back({s.h_data[slot] + s.h_desc[slot][k - i], reinterpret_cast<const uint8_t*>(ptr[k]), len[k],
+                        tee ? reinterpret_cast<uint8_t*>(tee[k]) : nullptr});
+      s.h_desc[slot][s.max_blocks + (k - i)] = len[k];
+      if (init) s.h_init[slot][k - i] = init[k];
     }
     copy_pool_run(s.pool, segs.data(), segs.size());
-    rc = submit(c, s, slot, j - i, used, max_len, nullptr, init != nullptr);
+    rc = submit(c, s, slot, j - i, g.used, g.max_len, nullptr, init != nullptr);
     if (rc) return rc;
     jobs[slot].busy = true;
     jobs[slot].first = i;
@@ -409,7 +406,7 @@ int kvsep_crc32c_batch_host_span(kvsep_crc32c_ctx* c, const char* host_base, uin
   int slot = 0;
   uint64_t i = 0;
   while (i < count) {
-    if (len[i] > s.bytes) {  // long block: chained segments
+    if (slots::is_long(len[i], s.bytes)) {  // long block: chained segments
       uint32_t r = 0;
       rc = big_block(c, s, jobs, out, base + off[i], len[i], init ? init[i] : 0u, pinned, &r);
       if (rc) return rc;
@@ -418,18 +415,13 @@ int kvsep_crc32c_batch_host_span(kvsep_crc32c_ctx* c, const char* host_base, uin
       continue;
     }
     // group consecutive blocks whose covering range fits one slot
-    uint64_t lo = off[i], hi = off[i] + len[i], j = i + 1, max_len = len[i];
-    while (j < count && j - i < s.max_blocks && len[j] <= s.bytes) {
-      const uint64_t nlo = std::min(lo, off[j]), nhi = std::max(hi, off[j] + len[j]);
-      if (nhi - nlo > s.bytes) break;
-      lo = nlo; hi = nhi; max_len = std::max(max_len, len[j]);
-      ++j;
-    }
+    const slots::SpanGroup g = slots::span_group(off, len, i, count, s.bytes, s.max_blocks);
+    const uint64_t lo = g.lo, hi = g.hi, j = g.j, max_len = g.max_len;
     rc = retire(s, slot, jobs[slot], out);
     if (rc) return rc;
     const uint64_t nblk = j - i;
     for (uint64_t k = 0; k < nblk; ++k) {
-      s.h_desc[slot][k] = off[i + k] - lo;
+      s.h_desc[slot][k] = slots::span_at(off[i + k], g);
       s.h_desc[slot][s.max_blocks + k] = len[i + k];
       if (init) s.h_init[slot][k] = init[i + k];
     }
