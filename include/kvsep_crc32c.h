@@ -237,6 +237,29 @@ int kvsep_log_frame_host(kvsep_crc32c_ctx* ctx, const char* const* payload, cons
  * that record and every later record of the same block get accept[i] = 0.  Returns the bytes reported as
  * dropped with "checksum mismatch" (header of the bad record to the end of its block, or of the file). */
 uint64_t kvsep_log_accept(const uint64_t* off, const uint8_t* ok, uint64_t count, uint64_t n, uint8_t* accept);
+/* kvsep_log_accept plus the reader events that leave no physical record behind.  ReadPhysicalRecord also returns
+ * kBadRecord, without a checksum, for a record length past its block ("bad record length", db/log_reader.cc:224-230)
+ * and for a preallocated zero header (:237-243); kvsep_log_walk only stops walking that block there.  In ReadRecord
+ * every kBadRecord abandons a fragmented record in progress (:153-159), so a caller that assembles FIRST / MIDDLE /
+ * LAST fragments from accept[] alone can join fragments across such a hole into a record log::Reader never returns.
+ * This call re-reads the headers of the host image buf[0, n) (the image kvsep_log_walk walked; ok[i] / count = its
+ * records and their checksum verdicts) and gives, besides accept[i] and the return value of kvsep_log_accept,
+ *   gap[i] (nullable) = 1 when such an event lies between record i-1 and record i: reset the assembly before record i;
+ *   *bad_length_bytes (nullable) = the bytes the reader reports with "bad record length" (only for blocks read in
+ *   full: in a short last block the reader takes a long record for a torn write, :231-234).
+ * It also knows the two type bytes that ReadPhysicalRecord's return value (:270-271, the type byte itself) turns into
+ * the reader's own codes (db/log_reader.h:66,72): a record of type 5 with a good checksum reads as kEof, so log::Reader
+ * stops there -- accept = 0 for it and for every later record, and nothing after it is counted; type 6 reads as a
+ * kBadRecord nobody reports -- accept = 0.  kvsep_log_accept, which sees no types, accepts both.
+ * Assembly, as log::Reader::ReadRecord does it (type[] from kvsep_log_walk; payload i = [off[i] + 1, off[i] + len[i])):
+ *   for each i:  if (gap[i] || !accept[i]) drop the record in progress;
+ *                if (!accept[i]) continue;
+ *                FULL: drop the record in progress, return payload i;   FIRST: start a record with payload i;
+ *                MIDDLE / LAST: if a record is in progress, append payload i (LAST: and return it);
+ *                any other type: drop the record in progress ("unknown record type").
+ *   A record still in progress at the end of the image is dropped (:144-151). */
+uint64_t kvsep_log_accept_gaps(const char* buf, uint64_t n, const uint8_t* ok, uint64_t count, uint8_t* accept,
+                               uint8_t* gap, uint64_t* bad_length_bytes);
 /* SST block trailers (table/table_builder.cc:209-232): masked_out[i] = Mask(Extend(Value(block_i), &types[i], 1)),
  * the LE32 word written after the type byte.  Device pointers, async on stream. */
 int kvsep_sst_trailers_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, const uint64_t* off,

@@ -46,11 +46,40 @@ constexpr uint64_t kVlogHeader = 8;       // db/log_format.h:40
 constexpr uint64_t kLogBlock = 32768;     // db/log_format.h:30
 constexpr uint64_t kLogHeader = 7;        // db/log_format.h:33
 constexpr uint64_t kSstTrailer = 5;       // table/format.h:81 kBlockTrailerSize
+constexpr uint8_t kLogEofCode = 5;        // db/log_reader.h:66,72: kEof = kMaxRecordType + 1, kBadRecord = + 2 share
+constexpr uint8_t kLogBadRecordCode = 6;  // the value space of the type byte ReadPhysicalRecord returns
 
 // Every invalid-argument return posts its reason first, so kvsep_last_error() never carries a stale message.
 inline int einval(const char* why) {
   kvsep::set_last_error(why);
   return KVSEP_EINVAL;
+}
+
+// One pass over a log image the way ReadPhysicalRecord (db/log_reader.cc:189-272) parses it: rec(p, l, t) for every
+// physical record whose header at p fits its block, skip(p, end, zero) where the reader drops the rest [p, end) of a
+// block without looking at a checksum -- a length past the block end (:224-235, zero = false) or a preallocated zero
+// header (:237-243, zero = true).  Both are kBadRecord to ReadRecord, unless the block is the short last one.
+template <class Rec, class Skip>
+inline void log_scan(const char* buf, uint64_t n, Rec rec, Skip skip) {
+  for (uint64_t blk = 0; blk < n; blk += kLogBlock) {
+    const uint64_t end = blk + kLogBlock < n ? blk + kLogBlock : n;
+    uint64_t p = blk;
+    while (end - p >= kLogHeader) {  // :192-215: < 7 bytes left = block trailer
+      const uint8_t* h = reinterpret_cast<const uint8_t*>(buf + p);
+      const uint64_t l = uint64_t(h[4]) | (uint64_t(h[5]) << 8);
+      const uint8_t t = h[6];
+      if (kLogHeader + l > end - p) {  // bad record length: drop rest of block
+        skip(p, end, false);
+        break;
+      }
+      if (t == 0 && l == 0) {  // preallocated zero region
+        skip(p, end, true);
+        break;
+      }
+      rec(p, l, t);
+      p += kLogHeader + l;
+    }
+  }
 }
 
 }  // namespace
@@ -128,25 +157,18 @@ int kvsep_vlog_frame_host(kvsep_crc32c_ctx* ctx, const char* const* payload, con
 uint64_t kvsep_log_walk(const char* buf, uint64_t n, uint64_t* off, uint64_t* len, uint32_t* stored, uint8_t* type,
                         uint64_t cap) {
   uint64_t k = 0;
-  for (uint64_t blk = 0; blk < n; blk += kLogBlock) {
-    const uint64_t end = blk + kLogBlock < n ? blk + kLogBlock : n;
-    uint64_t p = blk;
-    while (end - p >= kLogHeader) {  // db/log_reader.cc:195-220: < 7 bytes left = block trailer
-      const uint8_t* h = reinterpret_cast<const uint8_t*>(buf + p);
-      const uint64_t l = uint64_t(h[4]) | (uint64_t(h[5]) << 8);
-      const uint8_t t = h[6];
-      if (kLogHeader + l > end - p) break;      // :229-241 bad record length: drop rest of block
-      if (t == 0 && l == 0) break;               // :243-249 preallocated zero region
-      if (k < cap) {
-        if (off) off[k] = p + 6;                 // CRC covers type || payload (:247-248)
-        if (len) len[k] = 1 + l;
-        if (stored) stored[k] = le32(buf + p);
-        if (type) type[k] = t;
-      }
-      ++k;
-      p += kLogHeader + l;
-    }
-  }
+  log_scan(
+      buf, n,
+      [&](uint64_t p, uint64_t l, uint8_t t) {
+        if (k < cap) {
+          if (off) off[k] = p + 6;  // CRC covers type || payload (:247-248)
+          if (len) len[k] = 1 + l;
+          if (stored) stored[k] = le32(buf + p);
+          if (type) type[k] = t;
+        }
+        ++k;
+      },
+      [](uint64_t, uint64_t, bool) {});
   return k;
 }
 
@@ -295,6 +317,46 @@ uint64_t kvsep_log_accept(const uint64_t* off, const uint8_t* ok, uint64_t count
     dropped += end - hdr;  // drop_size = buffer_.size() (:255-257)
     dead_block = blk;
   }
+  return dropped;
+}
+
+uint64_t kvsep_log_accept_gaps(const char* buf, uint64_t n, const uint8_t* ok, uint64_t count, uint8_t* accept,
+                               uint8_t* gap, uint64_t* bad_length_bytes) {
+  uint64_t k = 0, dropped = 0, bad_length = 0, dead_block = ~0ull;
+  bool pending = false;  // a kBadRecord without a physical record since the last record
+  bool stopped = false;  // the reader returned kEof: nothing after it is read
+  log_scan(
+      buf, n,
+      [&](uint64_t p, uint64_t, uint8_t t) {
+        const uint64_t i = k++, blk = p / kLogBlock;
+        if (i >= count) return;
+        if (stopped || blk == dead_block) {  // never read, or already dropped with the buffer
+          accept[i] = 0;
+          if (gap) gap[i] = 0;
+          return;
+        }
+        if (gap) gap[i] = pending ? 1 : 0;
+        pending = false;
+        if (!ok[i]) {
+          accept[i] = 0;
+          const uint64_t end = (blk + 1) * kLogBlock < n ? (blk + 1) * kLogBlock : n;
+          dropped += end - p;  // drop_size = buffer_.size() (:255-257)
+          dead_block = blk;
+        } else if (t == kLogEofCode) {  // :270-271 returns the type byte itself: 5 reads as kEof
+          accept[i] = 0;
+          stopped = true;
+        } else {
+          accept[i] = t == kLogBadRecordCode ? 0 : 1;  // ... and 6 as a kBadRecord nobody reports
+        }
+      },
+      [&](uint64_t p, uint64_t end, bool zero) {
+        const uint64_t blk = p / kLogBlock;
+        if (stopped || blk == dead_block) return;  // the reader never parsed this far
+        pending = true;
+        // reported only while eof_ is unset, i.e. when the block was read in full (:227-235)
+        if (!zero && end - blk * kLogBlock == kLogBlock) bad_length += end - p;
+      });
+  if (bad_length_bytes) *bad_length_bytes = bad_length;
   return dropped;
 }
 

@@ -119,6 +119,8 @@ _SIGS = {
                                             ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     "kvsep_log_accept": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
                                            ctypes.c_void_p]),
+    "kvsep_log_accept_gaps": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kvsep_sst_trailers_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                                  ctypes.c_uint64, ctypes.c_uint64]),
@@ -652,6 +654,21 @@ def log_accept(off, ok, n: int):
     dropped = lib().kvsep_log_accept(off.ctypes.data_as(ctypes.c_void_p), ok.ctypes.data_as(ctypes.c_void_p),
                                      off.size, n, acc.ctypes.data_as(ctypes.c_void_p))
     return acc[:off.size], int(dropped)
+
+
+def log_accept_gaps(image, ok):
+    """kvsep_log_accept_gaps over the host image log_walk walked and its records' checksum verdicts -> (accept, gap,
+    bytes reported with "checksum mismatch", bytes reported with "bad record length"); gap[i] = 1 where the reader
+    met a bad record length or a zero header between record i-1 and record i (reset the assembly there)."""
+    p, keep = _buf(image)
+    ok = np.ascontiguousarray(ok, dtype=np.uint8)
+    acc = np.zeros(max(ok.size, 1), np.uint8)
+    gap = np.zeros(max(ok.size, 1), np.uint8)
+    bad_len = ctypes.c_uint64()
+    dropped = lib().kvsep_log_accept_gaps(p, keep.nbytes, ok.ctypes.data_as(ctypes.c_void_p), ok.size,
+                                          acc.ctypes.data_as(ctypes.c_void_p), gap.ctypes.data_as(ctypes.c_void_p),
+                                          ctypes.byref(bad_len))
+    return acc[:ok.size], gap[:ok.size], int(dropped), int(bad_len.value)
 
 
 def partition(length, parts: int) -> np.ndarray:

@@ -49,6 +49,52 @@ def log_image(records, oracle):
     return bytes(out), phys
 
 
+_FNV = {}
+
+
+def fnv64(b: bytes) -> str:
+    """The record identity of tests/golden/*.json (FNV-1a 64, independent of the CRC under test); cached per content,
+    since most records of a damaged file are those of the intact one."""
+    h = _FNV.get(b)
+    if h is None:
+        x = 0xCBF29CE484222325
+        for c in b:
+            x = ((x ^ c) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
+        h = _FNV[b] = "%016x" % x
+    return h
+
+
+def assemble(img, off, ln, ty, accept, gap=None):
+    """log::Reader::ReadRecord (db/log_reader.cc:58-173) over the physical records of kvsep_log_walk: FULL returns,
+    FIRST/MIDDLE/LAST assemble; a dropped record (accept 0), a reader event without a record before this one
+    (gap 1: bad record length or zero header, kvsep_log_accept_gaps) and an unknown type each abandon the record in
+    progress, as kBadRecord / "unknown record type" do.  -> [[len, fnv64], ...] of the logical records."""
+    out, scratch, infrag = [], b"", False
+    if gap is None:
+        gap = [0] * len(accept)
+    for o, n, t, a, g in zip(off, ln, ty, accept, gap):
+        frag = img[int(o) + 1:int(o) + int(n)]  # off points at the type byte, len = 1 + payload
+        if g or not a:
+            infrag, scratch = False, b""
+        if not a:
+            continue
+        if t == FULL:
+            infrag, scratch = False, b""
+            out.append(frag)
+        elif t == FIRST:
+            scratch, infrag = frag, True
+        elif t == MIDDLE:
+            if infrag:
+                scratch += frag
+        elif t == LAST:
+            if infrag:
+                out.append(scratch + frag)
+                infrag, scratch = False, b""
+        else:
+            infrag, scratch = False, b""
+    return [[len(r), fnv64(r)] for r in out]
+
+
 def sst_image(blocks, types, oracle):
     """TableBuilder::WriteRawBlock (table/table_builder.cc:209-232): block, then [type][Mask(crc)]
     with crc = Extend(Value(block), &type, 1).  Returns (image, offsets, trailer words)."""

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import kvsep
+from framing_builders import assemble, fnv64
 from kvsep import splitmix64_bytes
 
 pytestmark = pytest.mark.gpu
@@ -43,13 +44,6 @@ def ctx():
     c = kvsep.Context(0)
     yield c
     c.close()
-
-
-def fnv64(b: bytes) -> str:
-    h = 0xCBF29CE484222325
-    for x in b:
-        h = ((h ^ x) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
-    return "%016x" % h
 
 
 def payloads(seed, lens):
@@ -127,29 +121,6 @@ def test_log_frame_matches_reference_writer(ctx, gold, manifest):
     assert hashlib.sha256(a + b).hexdigest() == gold["sha256"]["manifest.log"]
 
 
-def assemble(img, off, ln, ty, accept):
-    """log::Reader::ReadRecord (db/log_reader.cc:58-153) over the physical records: FULL returns, FIRST/MIDDLE/LAST
-    assemble, a dropped record (kBadRecord) abandons a record in progress."""
-    out, scratch, infrag = [], b"", False
-    for o, n, t, a in zip(off, ln, ty, accept):
-        frag = img[int(o) + 1:int(o) + int(n)]  # off points at the type byte, len = 1 + payload
-        if not a:
-            infrag, scratch = False, b""
-        elif t == 1:
-            infrag, scratch = False, b""
-            out.append(frag)
-        elif t == 2:
-            scratch, infrag = frag, True
-        elif t == 3:
-            if infrag:
-                scratch += frag
-        elif t == 4:
-            if infrag:
-                out.append(scratch + frag)
-                infrag, scratch = False, b""
-    return [[len(r), fnv64(r)] for r in out]
-
-
 @pytest.mark.parametrize("name", ["intact", "full_payload", "first_payload", "middle_payload", "last_payload",
                                   "type_byte", "length_field", "crc_after_reopen"])
 def test_log_verify_matches_reference_reader(ctx, gold, manifest, name):
@@ -165,7 +136,9 @@ def test_log_verify_matches_reference_reader(ctx, gold, manifest, name):
     ok = ctx.log_verify(img)
     accept, dropped = kvsep.log_accept(off, ok, len(img))
     assert dropped == mismatch_bytes(reader["drops"])
-    assert assemble(img, off, ln, ty, accept) == reader["records"]
+    accept2, gap, dropped2, _ = kvsep.log_accept_gaps(img, ok)
+    assert np.array_equal(accept2, accept) and dropped2 == dropped
+    assert assemble(img, off, ln, ty, accept, gap) == reader["records"]
 
 
 # ------------------------------------------------------------------ SST
