@@ -681,6 +681,8 @@ int launch_batch_body(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capt
   KVSEP_HIP(hipGetLastError());
   if (c->inject_failure) {  // fault injection (tests): fail between the CRC kernel and the combine kernel
     c->inject_failure = false;
+    if (e0) c->ev_pool.push_back(e0);  // the timing pair is not recorded: back to the pool
+    if (e1) c->ev_pool.push_back(e1);
     return set_err(KVSEP_EHIP, "injected failure after the CRC kernel (kvsep_crc32c_ctx_inject_failure)");
   }
   if (c->timing && e0 && e1) {

@@ -2,8 +2,9 @@
 VPCLMULQDQ fold, the SSE4.2 crc32 loop and the portable table-driven leg that any CPU runs, so Extend is total on any
 host as util/crc32c.cc's portable path is (/root/reference/util/crc32c.cc:276-377, gated by port/port_stdcxx.h:142-152).
 
-  * every length 0..1023 at every offset 0..15, init 0 and a random init, plus the reference's large-block goldens, on
-    each leg (KVSEP_HOST_CRC forces the slower legs, in a child process each: the leg is chosen once per process);
+  * every length 0..1023, and the lengths around the crc32 leg's 1 KiB and 4 KiB lane thresholds and their mixtures,
+    at every offset 0..15, init 0 and a random init, plus the reference's large-block goldens, on each leg
+    (KVSEP_HOST_CRC forces the slower legs, in a child process each: the leg is chosen once per process);
   * the leg the library reports (kvsep_crc32c_host_path) is the one the CPU supports, so a fold sweep cannot pass on
     the crc32 path without saying so (ADVICE r4);
   * host_crc.cpp built alone with KVSEP_HOST_NO_X86 -- the form a non-x86 host compiles -- contains no x86 CRC
@@ -30,15 +31,19 @@ import kvsep
 from kvsep import splitmix64_bytes
 oracle = load_oracle()
 f = kvsep.lib().kvsep_crc32c_extend_host
-data = splitmix64_bytes(1024 + 64, 2024, 0)
+data = splitmix64_bytes(65536 + 13 + 64, 2024, 0)
 rng = np.random.default_rng(5)
 bad = []
+# the crc32 leg's 3-way loop runs rounds of 3 x 4 KiB, 3 x 1 KiB and 3 x 256 B lanes: lengths around each threshold
+# (12288, 3072, 768; 0..1023 reaches the last only) and mixtures of the three lane sizes
+lanes = [3071, 3072, 3073, 3072 + 767, 3072 + 768, 3072 + 769, 4096, 12287, 12288, 12289] + \
+        [12288 + 3072 + 768 + k for k in (0, 7, 8, 9)] + [2 * 12288 + 5, 65536 + 13]
 for o in range(16):
-    for n in range(1024):
+    for n in list(range(1024)) + lanes:
         for init in (0, int(rng.integers(0, 2**32))):
             if f(init, data.ctypes.data + o, n) != oracle.extend_addr(init, data.ctypes.data + o, n):
                 bad.append((o, n, init))
-print(json.dumps({"path": kvsep.host_path(), "bad": bad[:10], "nbad": len(bad)}))
+print(json.dumps({"path": kvsep.host_path(), "bad": bad[:10], "nbad": len(bad), "cases": 16 * (1024 + len(lanes)) * 2}))
 """
 
 
@@ -65,18 +70,27 @@ def _run(leg):
 @pytest.mark.parametrize("leg", [None, "sse42", "portable"])
 def test_every_length_and_offset_on_each_leg(leg):
     out = _run(leg)
-    assert out["nbad"] == 0, out
-    flags = _cpu_flags()
-    best = ("fold" if {"avx512f", "vpclmulqdq", "pclmulqdq", "sse4_2"} <= flags else
-            "sse42" if "sse4_2" in flags else "portable")
-    expect = {None: best, "sse42": "sse42" if best != "portable" else "portable", "portable": "portable"}[leg]
+    assert out["nbad"] == 0 and out["cases"] == 16 * (1024 + 16) * 2, out
+    expect, best = _expected_path(leg)
     assert out["path"] == expect, (out, best)
 
 
-def test_large_blocks_on_the_portable_leg():
+def _expected_path(leg):
+    """(the leg a process asked for `leg` must report, the best leg of this CPU): on a CPU without SSE4.2 a request
+    for sse42 runs -- and reports -- the portable leg."""
+    flags = _cpu_flags()
+    best = ("fold" if {"avx512f", "vpclmulqdq", "pclmulqdq", "sse4_2"} <= flags else
+            "sse42" if "sse4_2" in flags else "portable")
+    return {None: best, "sse42": "sse42" if best != "portable" else "portable", "portable": "portable"}[leg], best
+
+
+@pytest.mark.parametrize("leg", ["portable", "sse42"])
+def test_large_blocks_on_each_slow_leg(leg):
     """The reference's 4 KiB ... 4 MiB + 1 goldens (tests/golden, computed by the compiled util/crc32c.cc) on the
-    portable leg, where the 8-byte table loop carries nearly every byte."""
-    from kvsep import workloads as W
+    portable leg, where the 8-byte table loop carries nearly every byte, and on the crc32 leg, where the 4 KiB lanes of
+    the 3-way loop and their shift tables do: the leg a host without VPCLMULQDQ runs for every SST block.  The reported
+    path is the requested one (on a CPU without SSE4.2 the sse42 case is the portable leg again), so the sse42 run
+    cannot pass on the fold."""
     body = r"""
 import json, os, sys
 sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
@@ -90,11 +104,13 @@ f = kvsep.lib().kvsep_crc32c_extend_host
 bad = [c for c in g["large"] if f(c["init"], data.ctypes.data + c["offset"], c["len"]) != c["crc"]]
 print(json.dumps({"path": kvsep.host_path(), "n": len(g["large"]), "bad": len(bad)}))
 """
-    env = dict(os.environ, KVSEP_HOST_CRC="portable")
+    env = dict(os.environ, KVSEP_HOST_CRC=leg)
     r = subprocess.run([sys.executable, "-c", body, ROOT], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
-    assert out["path"] == "portable" and out["n"] >= 10 and out["bad"] == 0, out
+    expect, best = _expected_path(leg)
+    assert out["path"] == expect, (out, f"asked for {leg}; this CPU's best leg is {best}")
+    assert out["n"] >= 10 and out["bad"] == 0, out
 
 
 def test_portable_only_build_has_no_x86_crc_and_is_exact(tmp_path, oracle):
