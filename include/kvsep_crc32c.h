@@ -36,7 +36,9 @@ extern "C" {
  * _capture_sets); the fault-injection hook left this header (csrc/kvsep_testing.h) and works only under
  * KVSEP_TEST_HOOKS=1; no signature changed.  ABI 4 later gained the list forms of the verify calls
  * (kvsep_crc32c_verify_list_device, kvsep_sst_verify_list_device / _host, kvsep_log_verify_device,
- * kvsep_crc32c_group_verify_list_device): new entry points only, no signature changed, so the version stays 4.
+ * kvsep_crc32c_group_verify_list_device): new entry points only, no signature changed, so the version stays 4; the
+ * combine, concat and gather forms (kvsep_crc32c_combine, kvsep_crc32c_concat_device, kvsep_crc32c_gather_device /
+ * _host, kvsep_crc32c_group_extend_host) came the same way.
  * The reference's C++ symbol leveldb::crc32c::Extend is not in this library: it is in the libkvsep_leveldb_abi.so
  * shim. */
 #define KVSEP_ABI_VERSION 4
@@ -185,8 +187,52 @@ int kvsep_crc32c_verify_list_device(kvsep_crc32c_ctx* ctx, void* stream, const v
                                     uint64_t bad_cap, uint8_t* ok, uint64_t count, uint64_t total_bytes,
                                     uint64_t max_len);
 
+/* ---------------------------------------------------------------- combine, concat and gather forms
+ * Value(X) = Extend(0, X).  For every byte string B and every c, Extend(c, B) = c * x^(8|B|) ^ Value(B) (products mod
+ * the CRC polynomial; Extend's pre- and post-inversion cancel), so the CRC of A||B follows from the CRCs of its parts
+ * -- what zlib's crc32_combine and RocksDB's Crc32cCombine give.  ABI 4 gained these as new entry points only. */
+/* Returns Extend(crc_a, B) for crc_b = Value(B), len_b = |B|: Value(A||B) when crc_a = Value(A).  Host only, pure,
+ * never fails, needs no device; exact for every len_b up to 2^64 - 1; len_b == 0 returns crc_a. */
+uint32_t kvsep_crc32c_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
+/* Batched combine on the device.  Block i is the run of segments j in [first[i], first[i + 1]), in order, and
+ *   out[i] = fold over the run of  acc = kvsep_crc32c_combine(acc, seg_crc[j], seg_len[j]),  acc = init ? init[i] : 0
+ * = Extend(init[i], the segments' bytes back to back) when seg_crc[j] = Value(segment j).  A block with no segments
+ * gives its init; a segment of length 0 leaves acc as it is.  Only CRCs and lengths are read, never payload: seg_len[j]
+ * may be anything up to 2^64 - 1.  All arrays are DEVICE pointers; asynchronous on `stream`; one kernel launch, no
+ * library scratch, no atomics, no verdict: needs no kvsep_crc32c_reserve and can be captured as it is.
+ * count <= 2^32 - 1, else KVSEP_EINVAL.
+ * Memory touched: first is read for exactly count + 1 elements and out is written for exactly count.  Every first[]
+ * value is clamped to nseg before use and a run that ends before it starts is empty, so seg_crc / seg_len are read at
+ * indices < nseg only, whatever first[] holds (with nseg == 0 they may be NULL); init is read for exactly count. */
+int kvsep_crc32c_concat_device(kvsep_crc32c_ctx* ctx, void* stream, const uint32_t* seg_crc, const uint64_t* seg_len,
+                               const uint64_t* first, const uint32_t* init, uint32_t* out, uint64_t count,
+                               uint64_t nseg);
+
+/* Gather (iovec) form: block i is the concatenation, in order, of the segments [base + seg_off[j], + seg_len[j]) for
+ * j in [first[i], first[i + 1]), which may lie anywhere -- out of order, overlapping, shared between blocks -- and
+ *   out[i] = Extend(init ? init[i] : 0, that concatenation),
+ * without the block being copied together first (a group-commit batch still lying as its members, a record as its
+ * FIRST / MIDDLE / LAST fragments).  It is kvsep_crc32c_batch_device over the nseg segments with no init, writing
+ * seg_crc[j] = Value(segment j) (the caller's array of nseg words, useful in its own right), followed on the same
+ * stream by kvsep_crc32c_concat_device.  total_bytes / max_len are the hints of kvsep_crc32c_batch_device applied to
+ * the segments, with its limits (nseg <= 2^32 - 1; 2^31 - 1 when planned); every route serves the segment pass.
+ * kvsep_crc32c_reserve(ctx, nseg, total_bytes) makes the call allocation-free and capturable.
+ * Memory touched: as kvsep_crc32c_batch_device for base / seg_off / seg_len over nseg segments (a segment of length 0
+ * is never dereferenced); seg_crc is written for exactly nseg elements; first, init and out as in
+ * kvsep_crc32c_concat_device; the payload and the descriptor arrays are never written. */
+int kvsep_crc32c_gather_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, const uint64_t* seg_off,
+                               const uint64_t* seg_len, const uint64_t* first, const uint32_t* init, uint32_t* seg_crc,
+                               uint32_t* out, uint64_t count, uint64_t nseg, uint64_t total_bytes, uint64_t max_len);
+/* Host-pointer gather form: segment j is [seg_ptr[j], + seg_len[j]) in host memory.  kvsep_crc32c_batch_host over the
+ * segments (pinned staging, as the batched host form), then the same fold on the host; blocking.  first[] is clamped
+ * as in the device form; a segment of length 0 is never dereferenced. */
+int kvsep_crc32c_gather_host(kvsep_crc32c_ctx* ctx, const uint32_t* init, const char* const* seg_ptr,
+                             const uint64_t* seg_len, const uint64_t* first, uint32_t* out, uint64_t count,
+                             uint64_t nseg);
+
 /* ---------------------------------------------------------------- batched host form
- * Host pointers.  Blocks are gathered into pinned staging, copied H2D, checksummed and the
+ * Host pointers. Blocks are gathered into pinned staging, copied H2D, checksummed and the
  * u32 results copied back, double-buffered over two streams; blocking. */
 int kvsep_crc32c_batch_host(kvsep_crc32c_ctx* ctx, const uint32_t* init, const char* const* ptr,
                             const uint64_t* len, uint32_t* out, uint64_t count);
@@ -322,6 +368,13 @@ int kvsep_crc32c_group_verify_host_span(kvsep_crc32c_group* g, const char* host_
                                         const uint64_t* off, const uint64_t* len, const uint32_t* init,
                                         const uint32_t* expected_masked, uint32_t* out, uint64_t* first_bad,
                                         uint64_t* nbad, uint64_t count);
+/* ONE buffer over the whole group: *out = Extend(init_crc, data, n).  Member p of N checksums bytes
+ * [floor(n p / N), floor(n (p + 1) / N)) -- cut wherever that falls, at any alignment -- as one block through its own
+ * host-span pipeline (its pinned staging, its PCIe link, its host thread bound to its node), and the host joins the N
+ * values with kvsep_crc32c_combine.  n == 0 gives init_crc; with n < N some parts are empty.  Blocking.  The one call a
+ * single large Extend needs to use every GPU the process holds. */
+int kvsep_crc32c_group_extend_host(kvsep_crc32c_group* g, uint32_t init_crc, const char* data, uint64_t n,
+                                   uint32_t* out);
 /* kvsep_vlog_verify_host with the checksums spread over the group. */
 int kvsep_vlog_verify_host_group(kvsep_crc32c_group* g, const char* buf, uint64_t n, uint64_t* nrecords,
                                  uint64_t* ngood, uint64_t* good_bytes, uint64_t* drop_bytes);

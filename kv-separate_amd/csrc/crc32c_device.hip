@@ -25,7 +25,7 @@
 //
 // One translation unit, in parts: crc32c_fold.inc (the shared device code), crc32c_wide.inc (the wide kernel),
 // crc32c_narrow.inc (the narrow kernels for short blocks), crc32c_support.inc (combine, plan, helpers),
-// crc32c_verdicts.inc (the list pass of the verify forms), then this
+// crc32c_verdicts.inc (the list pass of the verify forms), crc32c_concat.inc (the batched combine), then this
 // file's host side -- the context, kernel routing, launches and the device C ABI.  crc32c_hooks.inc holds the
 // measurement hook points (empty in the shipped library), crc32c_diag.inc the KVSEP_DIAG build's A/B forms.
 #include <hip/hip_runtime.h>
@@ -45,6 +45,7 @@
 #include "kvsep_testing.h"
 #include "kvsep_internal.h"
 #include "plan_size.h"
+#include "concat_run.h"
 
 namespace kvsep {
 
@@ -53,6 +54,7 @@ namespace kvsep {
 #include "crc32c_narrow.inc"   // crc32c_narrow_kernel, _claim_kernel, _sorted_kernel
 #include "crc32c_support.inc"  // combine, plan, SST helpers, generator, streaming read
 #include "crc32c_verdicts.inc" // the list pass of the verify forms: bad-block index list, per-block verdict bytes
+#include "crc32c_concat.inc"   // crc32c_concat_kernel: the batched combine of the concat and gather forms
 
 }  // namespace kvsep
 
@@ -1032,6 +1034,63 @@ int kvsep_sst_trailers_device(kvsep_crc32c_ctx* c, void* stream, const void* bas
                                                                           c->d_tabs);
   KVSEP_HIP(hipGetLastError());
   return KVSEP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// The batched combine on `s`: one launch, no scratch (crc32c_concat.inc).  The caller holds the context's mutex and has
+// checked the arguments.
+int launch_concat(kvsep_crc32c_ctx* c, hipStream_t s, const uint32_t* seg_crc, const uint64_t* seg_len,
+                  const uint64_t* first, const uint32_t* init, uint32_t* out, uint64_t count, uint64_t nseg) {
+  if (!count) return KVSEP_OK;
+  DeviceGuard dg(c->device);
+  KVSEP_HIP(dg.err);
+  constexpr uint64_t kPerWg = uint64_t(kConcatWaves) * concat::kWaveBlocks;
+  crc32c_concat_kernel<<<unsigned((count + kPerWg - 1) / kPerWg), kConcatThreads, 0, s>>>(seg_crc, seg_len, first, init,
+                                                                                          out, count, nseg, c->d_tabs);
+  KVSEP_HIP(hipGetLastError());
+  return KVSEP_OK;
+}
+
+int concat_args(const char* who, kvsep_crc32c_ctx* c, const void* seg_a, const void* seg_b, const uint64_t* first,
+                const uint32_t* out, uint64_t count, uint64_t nseg) {
+  const char* what = !c                                 ? "null ctx"
+                     : count && (!first || !out)        ? "null first or out"
+                     : nseg && (!seg_a || !seg_b)       ? "null segment array"
+                     : count > 0xffffffffull            ? "more than 2^32 - 1 blocks in one batch"
+                                                        : nullptr;
+  if (!what) return KVSEP_OK;
+  return set_err(KVSEP_EINVAL, (std::string(who) + ": " + what).c_str());
+}
+}  // namespace
+
+extern "C" {
+
+int kvsep_crc32c_concat_device(kvsep_crc32c_ctx* c, void* stream, const uint32_t* seg_crc, const uint64_t* seg_len,
+                               const uint64_t* first, const uint32_t* init, uint32_t* out, uint64_t count,
+                               uint64_t nseg) {
+  int rc = concat_args("kvsep_crc32c_concat_device", c, seg_crc, seg_len, first, out, count, nseg);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(c->mu);
+  return launch_concat(c, static_cast<hipStream_t>(stream), seg_crc, seg_len, first, init, out, count, nseg);
+}
+
+int kvsep_crc32c_gather_device(kvsep_crc32c_ctx* c, void* stream, const void* base, const uint64_t* seg_off,
+                               const uint64_t* seg_len, const uint64_t* first, const uint32_t* init, uint32_t* seg_crc,
+                               uint32_t* out, uint64_t count, uint64_t nseg, uint64_t total_bytes, uint64_t max_len) {
+  int rc = concat_args("kvsep_crc32c_gather_device", c, seg_off, seg_len, first, out, count, nseg);
+  if (rc) return rc;
+  if (nseg && !seg_crc) return set_err(KVSEP_EINVAL, "kvsep_crc32c_gather_device: null seg_crc");
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // the segment pass is the batched form itself, on whatever route its hints pick; the combine follows on the stream
+  if (nseg) {
+    rc = launch_batch(c, c->sc, s, base, seg_off, seg_len, nullptr, nullptr, seg_crc, nullptr, nullptr, nseg,
+                      total_bytes, max_len);
+    if (rc) return rc;
+  }
+  return launch_concat(c, s, seg_crc, seg_len, first, init, out, count, nseg);
 }
 
 }  // extern "C"

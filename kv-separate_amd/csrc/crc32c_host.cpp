@@ -22,6 +22,8 @@
 #include <string>
 
 #include "../../include/kvsep_crc32c.h"
+#include "concat_run.h"
+#include "gf2.h"
 #include "host_crc.h"
 #include "host_slots.h"
 #include "kvsep_internal.h"
@@ -460,6 +462,33 @@ int kvsep_crc32c_ctx_host_placement(kvsep_crc32c_ctx* c, int* device_node, int* 
 int kvsep_crc32c_batch_host(kvsep_crc32c_ctx* c, const uint32_t* init, const char* const* ptr, const uint64_t* len,
                             uint32_t* out, uint64_t count) {
   return kvsep::batch_host_tee(c, init, ptr, len, out, count, nullptr);
+}
+
+uint32_t kvsep_crc32c_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
+  return gf2::combine(crc_a, crc_b, len_b);
+}
+
+int kvsep_crc32c_gather_host(kvsep_crc32c_ctx* c, const uint32_t* init, const char* const* seg_ptr,
+                             const uint64_t* seg_len, const uint64_t* first, uint32_t* out, uint64_t count,
+                             uint64_t nseg) {
+  if (!c || (count && (!first || !out)) || (nseg && (!seg_ptr || !seg_len))) {
+    set_last_error("kvsep_crc32c_gather_host: null argument");
+    return KVSEP_EINVAL;
+  }
+  // every segment's Value through the staging pipeline, then the fold of crc32c_concat_kernel on the host, over the
+  // same clamped runs (concat_run.h)
+  std::vector<uint32_t> seg_crc(nseg);
+  if (nseg) {
+    const int rc = kvsep_crc32c_batch_host(c, nullptr, seg_ptr, seg_len, seg_crc.data(), nseg);
+    if (rc) return rc;
+  }
+  for (uint64_t i = 0; i < count; ++i) {
+    const concat::Run r = concat::clamp_run(first[i], first[i + 1], nseg);
+    uint32_t acc = init ? init[i] : 0u;
+    for (uint64_t j = r.s; j < r.e; ++j) acc = gf2::combine(acc, seg_crc[j], seg_len[j]);
+    out[i] = acc;
+  }
+  return KVSEP_OK;
 }
 
 void* kvsep_host_alloc_pinned(uint64_t bytes) {

@@ -93,6 +93,35 @@ inline void x2n_table(uint32_t* out) {
   for (int k = 1; k < 64; ++k) out[k] = mulmod(out[k - 1], out[k - 1]);
 }
 
+// x^n mod P for every 64-bit n: the product of x^(2^k) over the set bits of n.
+inline uint32_t xpow(uint64_t n) {
+  struct Table {
+    uint32_t sq[64];
+    Table() { x2n_table(sq); }
+  };
+  static const Table t;
+  uint32_t p = 0x80000000u;  // x^0
+  for (int k = 0; n; ++k, n >>= 1)
+    if (n & 1u) p = mulmod(p, t.sq[k]);
+  return p;
+}
+
+// X(n) = x^(8n) mod P, the multiplier of Z_n, exact for every 64-bit n: 8n itself loses its top three bits from
+// n = 2^61 up (the device's gf2_shift forms it and is only called with block lengths), so x^n is raised over the 64
+// bits of n and then squared three times.
+inline uint32_t xpow8(uint64_t n) {
+  uint32_t p = xpow(n);
+  for (int i = 0; i < 3; ++i) p = mulmod(p, p);
+  return p;
+}
+
+// The CRC of A||B from the CRCs of its parts: Extend(crc_a, B) = crc_a * X(|B|) ^ Value(B) with crc_b = Value(B),
+// len_b = |B|.  Extend's pre- and post-inversion cancel between the two sides, so no ~ appears; len_b = 0 gives crc_a
+// (Value of nothing is 0).
+inline uint32_t combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
+  return mulmod(crc_a, xpow8(len_b)) ^ crc_b;
+}
+
 // x^-1 mod P: P has constant term 1, so x * (P - 1)/x = P - 1 = 1 mod P.  In the reflected representation (P - 1)/x
 // is the constant without its x^0 bit (bit 31), every power moved down by one (bit 31 - i -> bit 32 - i: a left
 // shift) and x^31 (bit 0) from P's x^32.

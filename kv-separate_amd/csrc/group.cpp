@@ -229,6 +229,31 @@ int kvsep_vlog_verify_host_group(kvsep_crc32c_group* g, const char* buf, uint64_
   return KVSEP_OK;
 }
 
+// One buffer over the whole group: the blocks of the forms above are independent, one Extend is not -- its parts are
+// joined with the combine, R(A||B) = R(A) * X(|B|) ^ R(B).  Member p of N takes bytes [n p / N, n (p + 1) / N), cut
+// wherever that falls, as one block through its own host-span pipeline.
+int kvsep_crc32c_group_extend_host(kvsep_crc32c_group* g, uint32_t init_crc, const char* data, uint64_t n,
+                                   uint32_t* out) {
+  if (!g || !out || (!data && n)) {
+    kvsep::set_last_error("group_extend_host: bad argument");
+    return KVSEP_EINVAL;
+  }
+  const int parts = int(g->ctx.size());
+  std::vector<uint64_t> cut(parts + 1);
+  for (int p = 0; p <= parts; ++p) cut[p] = uint64_t((unsigned __int128)n * unsigned(p) / unsigned(parts));
+  std::vector<uint32_t> crc(parts, 0u);  // Value of each part; of an empty one, 0
+  const int rc = fan_out(g, true, [&](int i) {
+    const uint64_t off = 0, len = cut[i + 1] - cut[i];
+    if (!len) return int(KVSEP_OK);
+    return kvsep_crc32c_batch_host_span(g->ctx[i], data + cut[i], len, &off, &len, nullptr, &crc[i], 1);
+  });
+  if (rc) return rc;
+  uint32_t acc = init_crc;
+  for (int p = 0; p < parts; ++p) acc = kvsep_crc32c_combine(acc, crc[p], cut[p + 1] - cut[p]);
+  *out = acc;
+  return KVSEP_OK;
+}
+
 int kvsep_crc32c_group_batch_device(kvsep_crc32c_group* g, const void* const* base, const uint64_t* const* off,
                                     const uint64_t* const* len, const uint32_t* const* init, uint32_t* const* out,
                                     const uint64_t* count, const uint64_t* total_bytes, const uint64_t* max_len) {

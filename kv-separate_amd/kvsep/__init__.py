@@ -96,6 +96,12 @@ _SIGS = {
     "kvsep_log_verify_device": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_uint64, ctypes.c_uint64,
                                                ctypes.c_uint64]),
     "kvsep_crc32c_group_verify_list_device": (ctypes.c_int, [ctypes.c_void_p] * 14 + [ctypes.c_uint64]),
+    "kvsep_crc32c_combine": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
+    "kvsep_crc32c_concat_device": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_uint64, ctypes.c_uint64]),
+    "kvsep_crc32c_gather_device": (ctypes.c_int, [ctypes.c_void_p] * 9 + [ctypes.c_uint64] * 4),
+    "kvsep_crc32c_gather_host": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_uint64, ctypes.c_uint64]),
+    "kvsep_crc32c_group_extend_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                                      ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]),
     "kvsep_crc32c_batch_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_uint64]),
     "kvsep_crc32c_batch_host_span": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
@@ -231,6 +237,12 @@ def extend_host(init_crc: int, data, n: int | None = None) -> int:
     p, keep = _buf(data)
     n = _checked_len(keep, n)
     return lib().kvsep_crc32c_extend_host(init_crc & 0xFFFFFFFF, p, n)
+
+
+def combine(crc_a: int, crc_b: int, len_b: int) -> int:
+    """Extend(crc_a, B) from crc_b = Value(B) and len_b = |B| (kvsep_crc32c_combine): the CRC of A||B from the CRCs of
+    its parts.  Host only, exact for every len_b < 2**64."""
+    return lib().kvsep_crc32c_combine(crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF, len_b)
 
 
 def host_path() -> str:
@@ -409,6 +421,31 @@ class Context:
                "kvsep_log_verify_device")
         return ok
 
+    def concat_device(self, seg_crc, seg_len, first, out, init=None, count=None, nseg=None, stream=None):
+        """kvsep_crc32c_concat_device: out[i] = the fold of combine over segments [first[i], first[i + 1]) of seg_crc /
+        seg_len, starting at init[i] (0 without init).  Device tensors (or addresses, then count and nseg are needed);
+        first has count + 1 entries."""
+        count = int(first.numel()) - 1 if count is None else count
+        nseg = int(seg_len.numel()) if nseg is None else nseg
+        _check(lib().kvsep_crc32c_concat_device(self._h, _stream_handle(stream), _dptr(seg_crc), _dptr(seg_len),
+                                                _dptr(first), _dptr(init), _dptr(out), count, nseg),
+               "kvsep_crc32c_concat_device")
+        return out
+
+    def gather_device(self, base, seg_off, seg_len, first, seg_crc, out, init=None, count=None, nseg=None,
+                      total_bytes=None, max_len=0, stream=None):
+        """kvsep_crc32c_gather_device: out[i] = Extend(init[i], the segments [first[i], first[i + 1]) of base back to
+        back); seg_crc (nseg words) receives every segment's Value.  total_bytes / max_len: the hints of batch_device
+        over the segments."""
+        count = int(first.numel()) - 1 if count is None else count
+        nseg = int(seg_len.numel()) if nseg is None else nseg
+        if total_bytes is None:
+            total_bytes = int(seg_len.sum().item()) if nseg else 0
+        _check(lib().kvsep_crc32c_gather_device(self._h, _stream_handle(stream), _dptr(base), _dptr(seg_off),
+                                                _dptr(seg_len), _dptr(first), _dptr(init), _dptr(seg_crc), _dptr(out),
+                                                count, nseg, total_bytes, max_len), "kvsep_crc32c_gather_device")
+        return out
+
     def stream_read(self, src, nbytes: int, sink, stream=None):
         _check(lib().kvsep_stream_read_device(self._h, _stream_handle(stream), _dptr(src), nbytes, _dptr(sink)),
                "kvsep_stream_read_device")
@@ -444,6 +481,24 @@ class Context:
                                              out.ctypes.data_as(ctypes.c_void_p), n), "kvsep_crc32c_batch_host")
         return out
 
+    def gather_host(self, segments, first, init=None):
+        """kvsep_crc32c_gather_host: segments = list of bytes-like objects; block i is segments [first[i],
+        first[i + 1]) back to back -> uint32 array of len(first) - 1 CRCs."""
+        keep = [_buf(b) for b in segments]
+        n = len(segments)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[k[0].value for k in keep])
+        lens = np.array([k[1].nbytes for k in keep], dtype=np.uint64)
+        first = np.ascontiguousarray(first, dtype=np.uint64)
+        count = first.size - 1
+        out = np.zeros(max(count, 1), dtype=np.uint32)
+        ip = None
+        if init is not None:
+            init = np.ascontiguousarray(init, dtype=np.uint32)
+            ip = init.ctypes.data_as(ctypes.c_void_p)
+        vp = ctypes.c_void_p
+        _check(lib().kvsep_crc32c_gather_host(self._h, ip, ptrs, lens.ctypes.data_as(vp), first.ctypes.data_as(vp),
+                                              out.ctypes.data_as(vp), count, n), "kvsep_crc32c_gather_host")
+        return out[:count]
 
     # -- framings (vlog / log / SST call sites)
     def vlog_verify(self, image, with_drop=False):
@@ -725,6 +780,16 @@ class Group:
                                                          out.ctypes.data_as(vp), ctypes.byref(fb), ctypes.byref(nb),
                                                          off.size), "kvsep_crc32c_group_verify_host_span")
         return out, fb.value, nb.value
+
+    def extend_host(self, init_crc: int, data, n: int | None = None) -> int:
+        """Extend(init_crc, data[:n]) of ONE buffer, each member checksumming 1 / size() of it
+        (kvsep_crc32c_group_extend_host)."""
+        p, keep = _buf(data)
+        n = _checked_len(keep, n)
+        out = ctypes.c_uint32()
+        _check(lib().kvsep_crc32c_group_extend_host(self._h, init_crc & 0xFFFFFFFF, p, n, ctypes.byref(out)),
+               "kvsep_crc32c_group_extend_host")
+        return out.value
 
     def vlog_verify(self, image):
         """kvsep_vlog_verify_host_group -> (records, good, good_bytes, drop_bytes)."""
