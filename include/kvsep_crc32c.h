@@ -38,7 +38,8 @@ extern "C" {
  * (kvsep_crc32c_verify_list_device, kvsep_sst_verify_list_device / _host, kvsep_log_verify_device,
  * kvsep_crc32c_group_verify_list_device): new entry points only, no signature changed, so the version stays 4; the
  * combine, concat and gather forms (kvsep_crc32c_combine, kvsep_crc32c_concat_device, kvsep_crc32c_gather_device /
- * _host, kvsep_crc32c_group_extend_host) came the same way.
+ * _host, kvsep_crc32c_group_extend_host) came the same way, and so did the device write side
+ * (kvsep_crc32c_pack_device, kvsep_vlog_frame_offsets, kvsep_vlog_frame_device, kvsep_sst_frame_device).
  * The reference's C++ symbol leveldb::crc32c::Extend is not in this library: it is in the libkvsep_leveldb_abi.so
  * shim. */
 #define KVSEP_ABI_VERSION 4
@@ -230,6 +231,53 @@ int kvsep_crc32c_gather_device(kvsep_crc32c_ctx* ctx, void* stream, const void* 
 int kvsep_crc32c_gather_host(kvsep_crc32c_ctx* ctx, const uint32_t* init, const char* const* seg_ptr,
                              const uint64_t* seg_len, const uint64_t* first, uint32_t* out, uint64_t count,
                              uint64_t nseg);
+
+/* ---------------------------------------------------------------- pack and frame forms (device write side)
+ * The CRC forms above checksum a block as its segments lie; these move its bytes, so that a batch resident on the
+ * device becomes the image the reference's writers would produce, ready for one pwrite.  ABI 4 gained them as new entry
+ * points only. */
+/* Batched gather-copy: block i is the segments j in [first[i], first[i + 1]), in order, each [base + seg_off[j],
+ * + seg_len[j]); their bytes go back to back to dst + dst_off[i].  Segments may lie anywhere -- out of order,
+ * overlapping, shared between blocks.  All arrays are DEVICE pointers; asynchronous on `stream`; one kernel launch
+ * (crc32c_pack_kernel), no library scratch, no atomics, no verdict: needs no kvsep_crc32c_reserve and can be captured as
+ * it is.  count <= 2^32 - 1, else KVSEP_EINVAL; a null ctx, or a null first / dst / dst_off with count != 0, or a null
+ * seg_off / seg_len with nseg != 0, is KVSEP_EINVAL before any device is touched.
+ * Memory touched.  Writes are byte-exact: block i writes [dst + dst_off[i], + len_i), len_i = the sum of its run's
+ * seg_len, and no other byte -- no edge is written through a wider word, so blocks may sit back to back at any
+ * alignment.  A block that does not lie wholly inside [0, dst_bytes) (its length may leave 64 bits) is not written at
+ * all.  Reads stay inside the naturally aligned 16-B granules that hold a byte of a segment of the batch; a segment of
+ * length 0 is never dereferenced.  first is read for exactly count + 1 elements, every value clamped to nseg and a run
+ * that ends before it starts empty, as in kvsep_crc32c_concat_device; dst_off for exactly count; seg_off / seg_len at
+ * indices < nseg only (with nseg == 0 they may be NULL).  The destination ranges of different blocks must not overlap
+ * each other or any segment: where they do, the bytes written are unspecified (the ranges written are not). */
+int kvsep_crc32c_pack_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, const uint64_t* seg_off,
+                             const uint64_t* seg_len, const uint64_t* first, void* dst, uint64_t dst_bytes,
+                             const uint64_t* dst_off, uint64_t count, uint64_t nseg);
+/* Offsets of vlog records laid back to back from `start`: rec_off[i] = start + sum over k < i of (8 + len[k]), *end
+ * (nullable) = start + the sum over all.  Host arrays, pure, no device.  KVSEP_EINVAL for a len over 2^32 - 1 (the
+ * header's LE32 length, db/value_log_writer.cc:48) or a sum that leaves 64 bits. */
+int kvsep_vlog_frame_offsets(const uint64_t* len, uint64_t count, uint64_t start, uint64_t* rec_off, uint64_t* end);
+/* vlog write side for device-resident members (VlogWriter::AddRecord, db/value_log_writer.cc:46-76): record i's payload
+ * is the segments [first[i], first[i + 1]) as in kvsep_crc32c_gather_device.  It is that call without init (seg_crc[j]
+ * = Value(segment j) for nseg words, crc_out[i] = Value(payload i) for count words), followed on the same stream by the
+ * gather-copy above, which also writes the header: dst + rec_off[i] holds [Mask(crc_out[i]) LE32][len_i LE32][payload].
+ * rec_off comes from kvsep_vlog_frame_offsets or the caller's own prefix sum.  The length word is the low 32 bits of
+ * len_i: a payload of 2^32 bytes or more is the caller's error.  total_bytes / max_len are the hints of the CRC pass
+ * over the segments, with its limits; kvsep_crc32c_reserve(ctx, nseg, total_bytes) makes the call allocation-free and
+ * capturable.  Memory touched: as the two calls; a record that does not lie inside [0, dst_bytes) is not written. */
+int kvsep_vlog_frame_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, const uint64_t* seg_off,
+                            const uint64_t* seg_len, const uint64_t* first, uint32_t* seg_crc, uint32_t* crc_out,
+                            void* dst, uint64_t dst_bytes, const uint64_t* rec_off, uint64_t count, uint64_t nseg,
+                            uint64_t total_bytes, uint64_t max_len);
+/* SST write side for device-resident blocks (TableBuilder::WriteRawBlock, table/table_builder.cc:209-232):
+ * kvsep_sst_trailers_device (masked_out[i] for count words), followed on the same stream by the gather-copy with block
+ * i = [base + off[i], + len[i]): dst + blk_off[i] holds [block][types[i]][masked_out[i] LE32], the bytes a handle
+ * (blk_off[i], len[i]) reads back.  Hints, limits and reserve(ctx, count, total_bytes) as kvsep_sst_trailers_device;
+ * types and masked_out are required, off / len / dst / blk_off when count != 0. */
+int kvsep_sst_frame_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, const uint64_t* off,
+                           const uint64_t* len, const uint8_t* types, uint32_t* masked_out, void* dst,
+                           uint64_t dst_bytes, const uint64_t* blk_off, uint64_t count, uint64_t total_bytes,
+                           uint64_t max_len);
 
 /* ---------------------------------------------------------------- batched host form
  * Host pointers. Blocks are gathered into pinned staging, copied H2D, checksummed and the

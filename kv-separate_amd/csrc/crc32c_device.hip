@@ -25,8 +25,8 @@
 //
 // One translation unit, in parts: crc32c_fold.inc (the shared device code), crc32c_wide.inc (the wide kernel),
 // crc32c_narrow.inc (the narrow kernels for short blocks), crc32c_support.inc (combine, plan, helpers),
-// crc32c_verdicts.inc (the list pass of the verify forms), crc32c_concat.inc (the batched combine), then this
-// file's host side -- the context, kernel routing, launches and the device C ABI.  crc32c_hooks.inc holds the
+// crc32c_verdicts.inc (the list pass of the verify forms), crc32c_concat.inc (the batched combine), crc32c_pack.inc
+// (the gather-copy of the pack and frame forms), then this file's host side -- the context, kernel routing, launches and the device C ABI.  crc32c_hooks.inc holds the
 // measurement hook points (empty in the shipped library), crc32c_diag.inc the KVSEP_DIAG build's A/B forms.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -46,6 +46,7 @@
 #include "kvsep_internal.h"
 #include "plan_size.h"
 #include "concat_run.h"
+#include "pack_run.h"
 
 namespace kvsep {
 
@@ -55,6 +56,7 @@ namespace kvsep {
 #include "crc32c_support.inc"  // combine, plan, SST helpers, generator, streaming read
 #include "crc32c_verdicts.inc" // the list pass of the verify forms: bad-block index list, per-block verdict bytes
 #include "crc32c_concat.inc"   // crc32c_concat_kernel: the batched combine of the concat and gather forms
+#include "crc32c_pack.inc"     // crc32c_pack_kernel: the byte-exact gather-copy of the pack and frame forms
 
 }  // namespace kvsep
 
@@ -1063,6 +1065,48 @@ int concat_args(const char* who, kvsep_crc32c_ctx* c, const void* seg_a, const v
   if (!what) return KVSEP_OK;
   return set_err(KVSEP_EINVAL, (std::string(who) + ": " + what).c_str());
 }
+
+// The gather form on `s`: the segment pass is the batched form itself, on whatever route its hints pick; the combine
+// follows on the stream.  The caller holds the context's mutex and has checked the arguments.
+int launch_gather(kvsep_crc32c_ctx* c, hipStream_t s, const void* base, const uint64_t* seg_off,
+                  const uint64_t* seg_len, const uint64_t* first, const uint32_t* init, uint32_t* seg_crc, uint32_t* out,
+                  uint64_t count, uint64_t nseg, uint64_t total_bytes, uint64_t max_len) {
+  if (nseg) {
+    int rc = launch_batch(c, c->sc, s, base, seg_off, seg_len, nullptr, nullptr, seg_crc, nullptr, nullptr, nseg,
+                          total_bytes, max_len);
+    if (rc) return rc;
+  }
+  return launch_concat(c, s, seg_crc, seg_len, first, init, out, count, nseg);
+}
+
+// The gather-copy on `s`: one launch, no scratch (crc32c_pack.inc).  The first part of the grid gives every
+// pack::kShortBlocks blocks a wavefront, the second every chunk of pack::kChunkBlocks blocks a team of workgroups --
+// about four workgroups per CU in all for a small batch (pack::team_size).  The caller holds the context's mutex and has
+// checked the arguments.
+template <typename F>
+int launch_pack(kvsep_crc32c_ctx* c, hipStream_t s, PackArgs a) {
+  if (!a.count) return KVSEP_OK;
+  DeviceGuard dg(c->device);
+  KVSEP_HIP(dg.err);
+  constexpr uint64_t kPerWg = uint64_t(kPackWaves) * pack::kShortBlocks;
+  a.short_wgs = uint32_t((a.count + kPerWg - 1) / kPerWg);
+  a.team = pack::team_size(a.count, 4u * uint32_t(c->num_cus > 0 ? c->num_cus : 256));
+  const uint64_t grid = a.short_wgs + pack::chunk_count(a.count) * a.team;  // < 2^29 for count < 2^32
+  crc32c_pack_kernel<F><<<unsigned(grid), kPackThreads, 0, s>>>(a);
+  KVSEP_HIP(hipGetLastError());
+  return KVSEP_OK;
+}
+
+int pack_args(const char* who, kvsep_crc32c_ctx* c, const uint64_t* seg_off, const uint64_t* seg_len,
+              const uint64_t* first, const void* dst, const uint64_t* dst_off, uint64_t count, uint64_t nseg) {
+  const char* what = !c                                       ? "null ctx"
+                     : count && (!first || !dst || !dst_off)  ? "null first, dst or offset array"
+                     : nseg && (!seg_off || !seg_len)         ? "null segment array"
+                     : count > 0xffffffffull                  ? "more than 2^32 - 1 blocks in one batch"
+                                                              : nullptr;
+  if (!what) return KVSEP_OK;
+  return set_err(KVSEP_EINVAL, (std::string(who) + ": " + what).c_str());
+}
 }  // namespace
 
 extern "C" {
@@ -1083,14 +1127,56 @@ int kvsep_crc32c_gather_device(kvsep_crc32c_ctx* c, void* stream, const void* ba
   if (rc) return rc;
   if (nseg && !seg_crc) return set_err(KVSEP_EINVAL, "kvsep_crc32c_gather_device: null seg_crc");
   std::lock_guard<std::mutex> g(c->mu);
+  return launch_gather(c, static_cast<hipStream_t>(stream), base, seg_off, seg_len, first, init, seg_crc, out, count,
+                       nseg, total_bytes, max_len);
+}
+
+int kvsep_crc32c_pack_device(kvsep_crc32c_ctx* c, void* stream, const void* base, const uint64_t* seg_off,
+                             const uint64_t* seg_len, const uint64_t* first, void* dst, uint64_t dst_bytes,
+                             const uint64_t* dst_off, uint64_t count, uint64_t nseg) {
+  int rc = pack_args("kvsep_crc32c_pack_device", c, seg_off, seg_len, first, dst, dst_off, count, nseg);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(c->mu);
+  return launch_pack<PackPlain>(c, static_cast<hipStream_t>(stream),
+                                PackArgs{static_cast<const uint8_t*>(base), seg_off, seg_len, first,
+                                         static_cast<uint8_t*>(dst), dst_bytes, dst_off, count, nseg, nullptr, nullptr,
+                                         0, 0});
+}
+
+int kvsep_vlog_frame_device(kvsep_crc32c_ctx* c, void* stream, const void* base, const uint64_t* seg_off,
+                            const uint64_t* seg_len, const uint64_t* first, uint32_t* seg_crc, uint32_t* crc_out,
+                            void* dst, uint64_t dst_bytes, const uint64_t* rec_off, uint64_t count, uint64_t nseg,
+                            uint64_t total_bytes, uint64_t max_len) {
+  int rc = pack_args("kvsep_vlog_frame_device", c, seg_off, seg_len, first, dst, rec_off, count, nseg);
+  if (rc) return rc;
+  if ((nseg && !seg_crc) || (count && !crc_out))
+    return set_err(KVSEP_EINVAL, "kvsep_vlog_frame_device: null seg_crc or crc_out");
+  std::lock_guard<std::mutex> g(c->mu);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // the segment pass is the batched form itself, on whatever route its hints pick; the combine follows on the stream
-  if (nseg) {
-    rc = launch_batch(c, c->sc, s, base, seg_off, seg_len, nullptr, nullptr, seg_crc, nullptr, nullptr, nseg,
-                      total_bytes, max_len);
-    if (rc) return rc;
-  }
-  return launch_concat(c, s, seg_crc, seg_len, first, init, out, count, nseg);
+  rc = launch_gather(c, s, base, seg_off, seg_len, first, nullptr, seg_crc, crc_out, count, nseg, total_bytes, max_len);
+  if (rc) return rc;
+  return launch_pack<PackVlog>(c, s,
+                               PackArgs{static_cast<const uint8_t*>(base), seg_off, seg_len, first,
+                                        static_cast<uint8_t*>(dst), dst_bytes, rec_off, count, nseg, crc_out, nullptr, 0,
+                                        0});
+}
+
+int kvsep_sst_frame_device(kvsep_crc32c_ctx* c, void* stream, const void* base, const uint64_t* off,
+                           const uint64_t* len, const uint8_t* types, uint32_t* masked_out, void* dst,
+                           uint64_t dst_bytes, const uint64_t* blk_off, uint64_t count, uint64_t total_bytes,
+                           uint64_t max_len) {
+  if (!c) return set_err(KVSEP_EINVAL, "kvsep_sst_frame_device: null ctx");
+  if (!types || !masked_out || (count && (!off || !len || !dst || !blk_off)))
+    return set_err(KVSEP_EINVAL, "kvsep_sst_frame_device: null argument");
+  if (count > 0xffffffffull)
+    return set_err(KVSEP_EINVAL, "kvsep_sst_frame_device: more than 2^32 - 1 blocks in one batch");
+  int rc = kvsep_sst_trailers_device(c, stream, base, off, len, types, masked_out, count, total_bytes, max_len);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(c->mu);
+  // block i is segment i: no first[]
+  return launch_pack<PackSst>(c, static_cast<hipStream_t>(stream),
+                              PackArgs{static_cast<const uint8_t*>(base), off, len, nullptr, static_cast<uint8_t*>(dst),
+                                       dst_bytes, blk_off, count, count, masked_out, types, 0, 0});
 }
 
 }  // extern "C"

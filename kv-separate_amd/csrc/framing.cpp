@@ -154,6 +154,21 @@ int kvsep_vlog_frame_host(kvsep_crc32c_ctx* ctx, const char* const* payload, con
   return kvsep::host_copy_parallel(ctx, at.data(), payload, len, count);  // the payload bytes
 }
 
+int kvsep_vlog_frame_offsets(const uint64_t* len, uint64_t count, uint64_t start, uint64_t* rec_off, uint64_t* end) {
+  if (count && (!len || !rec_off)) return einval("kvsep_vlog_frame_offsets: null argument");
+  uint64_t p = start;
+  for (uint64_t i = 0; i < count; ++i) {
+    if (len[i] > 0xffffffffull)  // db/value_log_writer.cc:48 (LE32 length)
+      return einval("kvsep_vlog_frame_offsets: payload longer than 2^32 - 1 bytes");
+    rec_off[i] = p;
+    const uint64_t rec = kVlogHeader + len[i];
+    if (p + rec < p) return einval("kvsep_vlog_frame_offsets: the offsets leave 64 bits");
+    p += rec;
+  }
+  if (end) *end = p;
+  return KVSEP_OK;
+}
+
 uint64_t kvsep_log_walk(const char* buf, uint64_t n, uint64_t* off, uint64_t* len, uint32_t* stored, uint8_t* type,
                         uint64_t cap) {
   uint64_t k = 0;

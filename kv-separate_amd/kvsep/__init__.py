@@ -100,6 +100,14 @@ _SIGS = {
     "kvsep_crc32c_concat_device": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_uint64, ctypes.c_uint64]),
     "kvsep_crc32c_gather_device": (ctypes.c_int, [ctypes.c_void_p] * 9 + [ctypes.c_uint64] * 4),
     "kvsep_crc32c_gather_host": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_uint64, ctypes.c_uint64]),
+    "kvsep_crc32c_pack_device": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_uint64, ctypes.c_void_p,
+                                                ctypes.c_uint64, ctypes.c_uint64]),
+    "kvsep_vlog_frame_offsets": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                                ctypes.c_void_p]),
+    "kvsep_vlog_frame_device": (ctypes.c_int, [ctypes.c_void_p] * 9 + [ctypes.c_uint64, ctypes.c_void_p] +
+                                [ctypes.c_uint64] * 4),
+    "kvsep_sst_frame_device": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_uint64, ctypes.c_void_p] +
+                               [ctypes.c_uint64] * 3),
     "kvsep_crc32c_group_extend_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                                                       ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]),
     "kvsep_crc32c_batch_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -446,6 +454,44 @@ class Context:
                                                 count, nseg, total_bytes, max_len), "kvsep_crc32c_gather_device")
         return out
 
+    def pack_device(self, base, seg_off, seg_len, first, dst, dst_bytes, dst_off, count=None, nseg=None, stream=None):
+        """kvsep_crc32c_pack_device: the bytes of segments [first[i], first[i + 1]) of base go back to back to dst +
+        dst_off[i], byte-exact; a block that does not lie inside [0, dst_bytes) is not written.  Device tensors (or
+        addresses, then count and nseg are needed); first has count + 1 entries."""
+        count = int(first.numel()) - 1 if count is None else count
+        nseg = int(seg_len.numel()) if nseg is None else nseg
+        _check(lib().kvsep_crc32c_pack_device(self._h, _stream_handle(stream), _dptr(base), _dptr(seg_off),
+                                              _dptr(seg_len), _dptr(first), _dptr(dst), dst_bytes, _dptr(dst_off),
+                                              count, nseg), "kvsep_crc32c_pack_device")
+        return dst
+
+    def vlog_frame_device(self, base, seg_off, seg_len, first, seg_crc, crc_out, dst, dst_bytes, rec_off, count=None,
+                          nseg=None, total_bytes=None, max_len=0, stream=None):
+        """kvsep_vlog_frame_device: gather_device without init (seg_crc, crc_out = Value of every segment / payload),
+        then dst + rec_off[i] = [Mask(crc_out[i])][len_i][payload i] (db/value_log_writer.cc:46-76); rec_off from
+        vlog_frame_offsets.  total_bytes / max_len: the hints of batch_device over the segments."""
+        count = int(first.numel()) - 1 if count is None else count
+        nseg = int(seg_len.numel()) if nseg is None else nseg
+        if total_bytes is None:
+            total_bytes = int(seg_len.sum().item()) if nseg else 0
+        _check(lib().kvsep_vlog_frame_device(self._h, _stream_handle(stream), _dptr(base), _dptr(seg_off),
+                                             _dptr(seg_len), _dptr(first), _dptr(seg_crc), _dptr(crc_out), _dptr(dst),
+                                             dst_bytes, _dptr(rec_off), count, nseg, total_bytes, max_len),
+               "kvsep_vlog_frame_device")
+        return dst
+
+    def sst_frame_device(self, base, off, length, types, masked_out, dst, dst_bytes, blk_off, count=None,
+                         total_bytes=None, max_len=0, stream=None):
+        """kvsep_sst_frame_device: sst_trailers_device (masked_out), then dst + blk_off[i] = [block i][types[i]]
+        [masked_out[i] LE32] (table/table_builder.cc:209-232)."""
+        count = int(off.numel()) if count is None else count
+        if total_bytes is None:
+            total_bytes = int(length.sum().item()) if count else 0
+        _check(lib().kvsep_sst_frame_device(self._h, _stream_handle(stream), _dptr(base), _dptr(off), _dptr(length),
+                                            _dptr(types), _dptr(masked_out), _dptr(dst), dst_bytes, _dptr(blk_off),
+                                            count, total_bytes, max_len), "kvsep_sst_frame_device")
+        return dst
+
     def stream_read(self, src, nbytes: int, sink, stream=None):
         _check(lib().kvsep_stream_read_device(self._h, _stream_handle(stream), _dptr(src), nbytes, _dptr(sink)),
                "kvsep_stream_read_device")
@@ -685,6 +731,19 @@ def vlog_walk(image):
     lib().kvsep_vlog_walk(p, keep.nbytes, off.ctypes.data_as(ctypes.c_void_p), ln.ctypes.data_as(ctypes.c_void_p),
                           st.ctypes.data_as(ctypes.c_void_p), cnt, ctypes.byref(used))
     return off, ln, st, used.value
+
+
+def vlog_frame_offsets(lens, start: int = 0):
+    """kvsep_vlog_frame_offsets: (rec_off, end) of vlog records of these payload lengths laid back to back from
+    `start`: rec_off[i] = start + sum(8 + lens[:i]), end = start + sum(8 + lens).  Host only; raises for a length over
+    2**32 - 1 or offsets that leave 64 bits."""
+    lens = np.ascontiguousarray(lens, dtype=np.uint64)
+    rec_off = np.zeros(lens.size, np.uint64)
+    end = ctypes.c_uint64()
+    vp = ctypes.c_void_p
+    _check(lib().kvsep_vlog_frame_offsets(lens.ctypes.data_as(vp), lens.size, start, rec_off.ctypes.data_as(vp),
+                                          ctypes.byref(end)), "kvsep_vlog_frame_offsets")
+    return rec_off, end.value
 
 
 def log_walk(image):
