@@ -39,7 +39,9 @@ extern "C" {
  * kvsep_crc32c_group_verify_list_device): new entry points only, no signature changed, so the version stays 4; the
  * combine, concat and gather forms (kvsep_crc32c_combine, kvsep_crc32c_concat_device, kvsep_crc32c_gather_device /
  * _host, kvsep_crc32c_group_extend_host) came the same way, and so did the device write side
- * (kvsep_crc32c_pack_device, kvsep_vlog_frame_offsets, kvsep_vlog_frame_device, kvsep_sst_frame_device).
+ * (kvsep_crc32c_pack_device, kvsep_vlog_frame_offsets, kvsep_vlog_frame_device, kvsep_sst_frame_device) and the
+ * offsets and salvage forms (kvsep_crc32c_offsets_device, kvsep_crc32c_salvage_device, kvsep_sst_salvage_device,
+ * kvsep_vlog_frame_auto_device).
  * The reference's C++ symbol leveldb::crc32c::Extend is not in this library: it is in the libkvsep_leveldb_abi.so
  * shim. */
 #define KVSEP_ABI_VERSION 4
@@ -113,7 +115,7 @@ int kvsep_crc32c_ctx_set_host_node(kvsep_crc32c_ctx* ctx, int node);
 int kvsep_crc32c_ctx_host_placement(kvsep_crc32c_ctx* ctx, int* device_node, int* staging_node, int* cpus, int cap);
 /* Pre-size scratch so later calls of up to `count` blocks / `total_bytes` bytes do not allocate: the context's own
  * scratch (eager calls) and every free capture set (at least 4 are made).  Required before graph capture; covers the
- * planned, narrow, verify, list and SST-verify forms: any batch within both numbers, whatever piece size it picks, and the SST
+ * planned, narrow, verify, list, SST-verify, offsets and salvage forms: any batch within both numbers, whatever piece size it picks, and the SST
  * read check called with the caller's own total_bytes. */
 int kvsep_crc32c_reserve(kvsep_crc32c_ctx* ctx, uint64_t count, uint64_t total_bytes);
 /* Graph capture (hipStreamBeginCapture ... EndCapture, torch.cuda.graph): every call captured into one graph runs on
@@ -278,6 +280,61 @@ int kvsep_sst_frame_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base
                            const uint64_t* len, const uint8_t* types, uint32_t* masked_out, void* dst,
                            uint64_t dst_bytes, const uint64_t* blk_off, uint64_t count, uint64_t total_bytes,
                            uint64_t max_len);
+
+/* ---------------------------------------------------------------- offsets and salvage forms (layout on the device)
+ * The pack and frame forms above take their destination offsets from the caller.  These compute them on the device
+ * from a verdict that is on the device, so that check -> choose -> lay out -> copy runs on one stream with no host step
+ * and can be captured.  ABI 4 gained them as new entry points only. */
+#define KVSEP_OFFSET_SKIP UINT64_MAX /* dst_off of a block that is not laid out */
+/* Masked offset scan.  Block i is the segments j in [first[i], first[i + 1]) of seg_len (first == NULL: block i is
+ * segment i), size_i the sum of their lengths.  The kept blocks are laid back to back from `start`, each taking
+ * head_bytes + size_i + tail_bytes:
+ *   dst_off[i] = start + the sum over kept k < i of (head_bytes + size_k + tail_bytes)   for a kept block,
+ *   dst_off[i] = KVSEP_OFFSET_SKIP                                                       for a dropped one,
+ *   *end       = start + the sum over every kept block,   *nkept (nullable) = the number of kept blocks.
+ * The keep rule is one of: keep[i] != 0 (a device u8 array: the ok[] of the list forms); i < *keep_before (a device u64:
+ * the *first_bad of a verify call, UINT64_MAX keeps all); neither: every block.  Passing both is KVSEP_EINVAL.
+ * Every sum saturates at 2^64 - 1: a kept block whose end reaches that value gets KVSEP_OFFSET_SKIP, and so does every
+ * kept block after it; *end is then UINT64_MAX (*nkept still counts them).  The pack forms write no block at
+ * KVSEP_OFFSET_SKIP (it lies inside no destination), so dst_off can be handed to them as it is.
+ * All arrays are DEVICE pointers; asynchronous on `stream`; three small kernels ordered by the stream (no atomics), on
+ * library scratch of 8 bytes per block sized by kvsep_crc32c_reserve(ctx, count, ...): a reserved call allocates nothing
+ * and can be captured; a captured call with more blocks than reserved fails with KVSEP_EINVAL before anything is
+ * enqueued.  count <= 2^32 - 1, else KVSEP_EINVAL.  The argument refusals come before any device is touched.
+ * Memory touched: first is read for exactly count + 1 elements, every value clamped to nseg and a run that ends before
+ * it starts empty, so seg_len is read at indices < nseg only (and only for kept blocks); keep for exactly count;
+ * *keep_before is read; dst_off is written for exactly count, *end and *nkept once. */
+int kvsep_crc32c_offsets_device(kvsep_crc32c_ctx* ctx, void* stream, const uint64_t* seg_len, const uint64_t* first,
+                                const uint8_t* keep, const uint64_t* keep_before, uint64_t head_bytes,
+                                uint64_t tail_bytes, uint64_t start, uint64_t* dst_off, uint64_t* end, uint64_t* nkept,
+                                uint64_t count, uint64_t nseg);
+/* Salvage copy: the kept blocks [base + off[i], + len[i]) go back to back to dst from offset 0.  It is the offsets pass
+ * above (block i = segment i, head = tail = 0, start = 0; the same keep rules), followed on the same stream by
+ * kvsep_crc32c_pack_device with the dst_off it wrote.  With keep_before = the first_bad of a verify call this is what
+ * VlogReader returns (db/value_log_reader.cc:109-122): everything before the first bad record.  dst_off (count words),
+ * *end and *nkept are outputs; a kept block that does not lie inside [0, dst_bytes) is not written (*end says what
+ * was needed); no byte of dst past *end is written. */
+int kvsep_crc32c_salvage_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, const uint64_t* off,
+                                const uint64_t* len, const uint8_t* keep, const uint64_t* keep_before, void* dst,
+                                uint64_t dst_bytes, uint64_t* dst_off, uint64_t* end, uint64_t* nkept, uint64_t count);
+/* SST salvage (RepairDB::ScanTable, db/repair.cc:220-260; paranoid compaction inputs): kvsep_sst_verify_list_device
+ * with ok[] (required; out, first_bad, nbad as there), then the offsets pass with keep = ok and tail = 5, then the
+ * gather-copy of len[i] + 5 bytes per passed block: dst holds the passed blocks with their trailers, contiguous from 0,
+ * dst_off[i] where block i went (a handle (dst_off[i], len[i]) reads it back), *end the bytes used.  Hints, limits and
+ * reserve(ctx, count, total_bytes) as kvsep_sst_verify_list_device. */
+int kvsep_sst_salvage_device(kvsep_crc32c_ctx* ctx, void* stream, const void* file_base, const uint64_t* off,
+                             const uint64_t* len, uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint8_t* ok,
+                             void* dst, uint64_t dst_bytes, uint64_t* dst_off, uint64_t* end, uint64_t* nkept,
+                             uint64_t count, uint64_t total_bytes, uint64_t max_len);
+/* kvsep_vlog_frame_device with the record offsets computed on the device: the gather pass, the offsets pass (head = 8,
+ * every record kept, from `start`) writing rec_off (count words, an output here) and *end, then the Vlog gather-copy.
+ * A payload over 2^32 - 1 bytes, which kvsep_vlog_frame_offsets refuses, gets KVSEP_OFFSET_SKIP, as does every record
+ * after it, and *end = UINT64_MAX: none of them is written.  reserve(ctx, max(count, nseg), total_bytes) makes the call
+ * allocation-free and capturable. */
+int kvsep_vlog_frame_auto_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, const uint64_t* seg_off,
+                                 const uint64_t* seg_len, const uint64_t* first, uint32_t* seg_crc, uint32_t* crc_out,
+                                 void* dst, uint64_t dst_bytes, uint64_t start, uint64_t* rec_off, uint64_t* end,
+                                 uint64_t count, uint64_t nseg, uint64_t total_bytes, uint64_t max_len);
 
 /* ---------------------------------------------------------------- batched host form
  * Host pointers. Blocks are gathered into pinned staging, copied H2D, checksummed and the

@@ -26,7 +26,7 @@
 // One translation unit, in parts: crc32c_fold.inc (the shared device code), crc32c_wide.inc (the wide kernel),
 // crc32c_narrow.inc (the narrow kernels for short blocks), crc32c_support.inc (combine, plan, helpers),
 // crc32c_verdicts.inc (the list pass of the verify forms), crc32c_concat.inc (the batched combine), crc32c_pack.inc
-// (the gather-copy of the pack and frame forms), then this file's host side -- the context, kernel routing, launches and the device C ABI.  crc32c_hooks.inc holds the
+// (the gather-copy of the pack and frame forms), crc32c_offsets.inc (the offsets pass of the salvage forms), then this file's host side -- the context, kernel routing, launches and the device C ABI.  crc32c_hooks.inc holds the
 // measurement hook points (empty in the shipped library), crc32c_diag.inc the KVSEP_DIAG build's A/B forms.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -47,6 +47,7 @@
 #include "plan_size.h"
 #include "concat_run.h"
 #include "pack_run.h"
+#include "offsets_run.h"
 
 namespace kvsep {
 
@@ -57,6 +58,7 @@ namespace kvsep {
 #include "crc32c_verdicts.inc" // the list pass of the verify forms: bad-block index list, per-block verdict bytes
 #include "crc32c_concat.inc"   // crc32c_concat_kernel: the batched combine of the concat and gather forms
 #include "crc32c_pack.inc"     // crc32c_pack_kernel: the byte-exact gather-copy of the pack and frame forms
+#include "crc32c_offsets.inc"  // offsets_*_kernel: the masked offset scan of the offsets and salvage forms
 
 }  // namespace kvsep
 
@@ -247,6 +249,25 @@ int ensure_list(Scratch& sc, uint64_t count, bool capturing = false) {
   KVSEP_HIP(hipMalloc(&sc.d_tile_cnt, nt * 4));
   KVSEP_HIP(hipMalloc(&sc.d_tile_base, nt * 8));
   sc.cap_tiles = nt;
+  return KVSEP_OK;
+}
+
+// The offsets pass's arrays (crc32c_offsets.inc): one extent per block; per tile of offsets::kTile blocks a sum, a kept
+// count and a base, then the two grand totals.
+int ensure_offsets(Scratch& sc, uint64_t count, bool capturing = false) {
+  if (count <= sc.cap_off) return KVSEP_OK;
+  if (capturing)
+    return set_err(KVSEP_EINVAL, "a captured offsets pass larger than kvsep_crc32c_reserve sized its capture set for");
+  int rc = quiesce(sc);
+  if (rc) return rc;
+  hipFree(sc.d_off_ext);
+  hipFree(sc.d_off_tile);
+  sc.d_off_ext = nullptr;
+  sc.d_off_tile = nullptr;
+  sc.cap_off = 0;
+  KVSEP_HIP(hipMalloc(&sc.d_off_ext, count * 8));
+  KVSEP_HIP(hipMalloc(&sc.d_off_tile, (3 * offsets::tile_count(count) + 2) * 8));
+  sc.cap_off = count;
   return KVSEP_OK;
 }
 
@@ -732,6 +753,8 @@ void free_scratch(Scratch& sc) {
   hipFree(sc.d_sst_stored);
   hipFree(sc.d_tile_cnt);
   hipFree(sc.d_tile_base);
+  hipFree(sc.d_off_ext);
+  hipFree(sc.d_off_tile);
   if (sc.last_use) (void)hipEventDestroy(sc.last_use);
   sc = Scratch();
 }
@@ -858,6 +881,8 @@ int reserve_scratch(kvsep_crc32c_ctx* c, Scratch& sc, uint64_t count, uint64_t t
   rc = ensure_vslot(sc, vslots_needed(c));
   if (rc) return rc;
   rc = ensure_list(sc, count);
+  if (rc) return rc;
+  rc = ensure_offsets(sc, count);
   if (rc) return rc;
   return ensure_plan(sc, count, plan::pieces_reserved(c->piece_bytes, c->piece_auto, c->num_cus, count, total_bytes));
 }
@@ -1183,10 +1208,10 @@ int kvsep_sst_frame_device(kvsep_crc32c_ctx* c, void* stream, const void* base, 
 
 namespace {
 // The SST read check, and its list form when `list` is given (the stored words are the ones the prep kernel extracts).
-int sst_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, const uint64_t* off,
+// The caller holds the context's mutex.
+int sst_verify_locked(kvsep_crc32c_ctx* c, void* stream, const void* file_base, const uint64_t* off,
                       const uint64_t* len, uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint64_t count,
                       uint64_t total_bytes, uint64_t max_len, const ListOut* list) {
-  std::lock_guard<std::mutex> g(c->mu);
   hipStream_t s = static_cast<hipStream_t>(stream);
   DeviceGuard dg(c->device);
   KVSEP_HIP(dg.err);
@@ -1220,9 +1245,208 @@ int sst_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, 
   }
   return capturing ? KVSEP_OK : release(sc, s);
 }
+
+int sst_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, const uint64_t* off,
+                      const uint64_t* len, uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint64_t count,
+                      uint64_t total_bytes, uint64_t max_len, const ListOut* list) {
+  std::lock_guard<std::mutex> g(c->mu);
+  return sst_verify_locked(c, stream, file_base, off, len, out, first_bad, nbad, count, total_bytes, max_len, list);
+}
+
+// ---- the offsets pass and the salvage forms built on it (crc32c_offsets.inc)
+
+// What an offsets pass is asked for; the scratch pointers are filled in by launch_offsets_in.
+struct OffsetsCall {
+  const uint64_t* seg_len;
+  const uint64_t* first;
+  const uint8_t* keep;
+  const uint64_t* keep_before;
+  uint64_t head, tail, start, max_size;
+  uint64_t* dst_off;
+  uint64_t* end;
+  uint64_t* nkept;
+  uint64_t count, nseg;
+};
+
+// The scratch the calls on `s` run on (the capture's own set under capture), checked to hold an offsets pass of `count`
+// blocks: refuses a captured call that was not reserved for before anything is enqueued, and allocates for an eager one.
+int offsets_scratch(kvsep_crc32c_ctx* c, hipStream_t s, uint64_t count, bool* capturing, Scratch** psc) {
+  int rc = stream_scratch(c, s, c->sc, capturing, psc);
+  if (rc) return rc;
+  return ensure_offsets(**psc, count, *capturing);
+}
+
+// The three kernels on `s`, on a scratch the caller has acquired and sized (ensure_offsets).  An empty batch runs the
+// write kernel alone, which then touches no scratch.
+int launch_offsets_in(Scratch& sc, hipStream_t s, const OffsetsCall& o) {
+  const uint64_t nt = offsets::tile_count(o.count);
+  OffsetsArgs a{};
+  a.seg_len = o.seg_len;
+  a.first = o.first;
+  a.keep = o.keep;
+  a.keep_before = reinterpret_cast<const unsigned long long*>(o.keep_before);
+  a.head = o.head, a.tail = o.tail, a.start = o.start, a.max_size = o.max_size;
+  a.count = o.count, a.nseg = o.nseg;
+  a.dst_off = o.dst_off, a.end = o.end, a.nkept = o.nkept;
+  if (nt) {
+    a.ext = sc.d_off_ext;
+    a.tile_sum = sc.d_off_tile;
+    a.tile_kept = sc.d_off_tile + nt;
+    a.tile_base = sc.d_off_tile + 2 * nt;
+    a.grand = sc.d_off_tile + 3 * nt;
+    offsets_tile_sum_kernel<<<unsigned(nt), offsets::kThreads, 0, s>>>(a);
+    KVSEP_HIP(hipGetLastError());
+    offsets_tile_scan_kernel<<<1, offsets::kScanThreads, 0, s>>>(a.tile_sum, a.tile_kept, a.tile_base, a.grand, nt);
+    KVSEP_HIP(hipGetLastError());
+  }
+  offsets_write_kernel<<<unsigned(nt ? nt : 1), offsets::kThreads, 0, s>>>(a);
+  KVSEP_HIP(hipGetLastError());
+  return KVSEP_OK;
+}
+
+// The offsets pass as a call of its own: its scratch is bracketed here.  `then`, when given, is enqueued inside the
+// bracket (a copy that reads the pass's scratch).  The caller holds the context's mutex.
+template <typename Then>
+int launch_offsets(kvsep_crc32c_ctx* c, hipStream_t s, const OffsetsCall& o, Then then) {
+  DeviceGuard dg(c->device);
+  KVSEP_HIP(dg.err);
+  bool capturing = false;
+  Scratch* psc = nullptr;
+  int rc = offsets_scratch(c, s, o.count, &capturing, &psc);
+  if (rc) return rc;
+  Scratch& sc = *psc;
+  rc = capturing ? KVSEP_OK : acquire(sc, s);
+  if (rc) return rc;
+  rc = launch_offsets_in(sc, s, o);
+  if (!rc) rc = then(sc);
+  if (rc) {
+    if (!capturing) (void)release(sc, s);
+    return rc;
+  }
+  return capturing ? KVSEP_OK : release(sc, s);
+}
+
+int launch_offsets(kvsep_crc32c_ctx* c, hipStream_t s, const OffsetsCall& o) {
+  return launch_offsets(c, s, o, [](Scratch&) { return KVSEP_OK; });
+}
+
+// Refusals shared by the offsets and salvage forms, before the context is looked at (so they hold on a machine with no
+// device): both keep rules at once, more blocks than a u32 index, a missing output.
+int offsets_args(const char* who, const void* keep, const void* keep_before, const void* dst_off, const void* end,
+                 uint64_t count) {
+  const char* what = keep && keep_before           ? "both keep and keep_before given: one keep rule at most"
+                     : count > 0xffffffffull       ? "more than 2^32 - 1 blocks in one batch"
+                     : !end || (count && !dst_off) ? "null dst_off or end"
+                                                   : nullptr;
+  if (!what) return KVSEP_OK;
+  return set_err(KVSEP_EINVAL, (std::string(who) + ": " + what).c_str());
+}
 }  // namespace
 
 extern "C" {
+
+int kvsep_crc32c_offsets_device(kvsep_crc32c_ctx* c, void* stream, const uint64_t* seg_len, const uint64_t* first,
+                                const uint8_t* keep, const uint64_t* keep_before, uint64_t head_bytes,
+                                uint64_t tail_bytes, uint64_t start, uint64_t* dst_off, uint64_t* end, uint64_t* nkept,
+                                uint64_t count, uint64_t nseg) {
+  const char* who = "kvsep_crc32c_offsets_device";
+  int rc = offsets_args(who, keep, keep_before, dst_off, end, count);
+  if (rc) return rc;
+  if (nseg && !seg_len) return set_err(KVSEP_EINVAL, "kvsep_crc32c_offsets_device: null seg_len");
+  if (!c) return set_err(KVSEP_EINVAL, "kvsep_crc32c_offsets_device: null ctx");
+  std::lock_guard<std::mutex> g(c->mu);
+  return launch_offsets(c, static_cast<hipStream_t>(stream),
+                        OffsetsCall{seg_len, first, keep, keep_before, head_bytes, tail_bytes, start, ~uint64_t(0),
+                                    dst_off, end, nkept, count, nseg});
+}
+
+int kvsep_crc32c_salvage_device(kvsep_crc32c_ctx* c, void* stream, const void* base, const uint64_t* off,
+                                const uint64_t* len, const uint8_t* keep, const uint64_t* keep_before, void* dst,
+                                uint64_t dst_bytes, uint64_t* dst_off, uint64_t* end, uint64_t* nkept, uint64_t count) {
+  int rc = offsets_args("kvsep_crc32c_salvage_device", keep, keep_before, dst_off, end, count);
+  if (rc) return rc;
+  if (count && (!off || !len || !dst)) return set_err(KVSEP_EINVAL, "kvsep_crc32c_salvage_device: null off, len or dst");
+  if (!c) return set_err(KVSEP_EINVAL, "kvsep_crc32c_salvage_device: null ctx");
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  rc = launch_offsets(c, s, OffsetsCall{len, nullptr, keep, keep_before, 0, 0, 0, ~uint64_t(0), dst_off, end, nkept,
+                                        count, count});
+  if (rc) return rc;
+  // block i is segment i: no first[]; a dropped block's kSkip lies in no destination (pack::fits)
+  return launch_pack<PackPlain>(c, s,
+                                PackArgs{static_cast<const uint8_t*>(base), off, len, nullptr,
+                                         static_cast<uint8_t*>(dst), dst_bytes, dst_off, count, count, nullptr, nullptr,
+                                         0, 0});
+}
+
+int kvsep_sst_salvage_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, const uint64_t* off,
+                             const uint64_t* len, uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint8_t* ok,
+                             void* dst, uint64_t dst_bytes, uint64_t* dst_off, uint64_t* end, uint64_t* nkept,
+                             uint64_t count, uint64_t total_bytes, uint64_t max_len) {
+  int rc = offsets_args("kvsep_sst_salvage_device", nullptr, nullptr, dst_off, end, count);
+  if (rc) return rc;
+  if (!file_base || !off || !len || !out || !ok || (count && !dst))
+    return set_err(KVSEP_EINVAL, "kvsep_sst_salvage_device: null argument");
+  if (!c) return set_err(KVSEP_EINVAL, "kvsep_sst_salvage_device: null ctx");
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  {  // refused before anything is enqueued (the read check makes its own checks first thing, too)
+    DeviceGuard dg(c->device);
+    KVSEP_HIP(dg.err);
+    bool capturing = false;
+    Scratch* psc = nullptr;
+    rc = offsets_scratch(c, s, count, &capturing, &psc);
+    if (rc) return rc;
+  }
+  const ListOut l{nullptr, 0, ok};
+  rc = sst_verify_locked(c, stream, file_base, off, len, out, first_bad, nbad, count, total_bytes, max_len, &l);
+  if (rc) return rc;
+  // A kept block's extent is its bytes plus the 5-byte trailer that follows them in the file, a dropped one's is 0: the
+  // pass's extent array is the length array of the copy, which therefore runs inside the pass's scratch bracket.
+  return launch_offsets(c, s, OffsetsCall{len, nullptr, ok, nullptr, 0, 5, 0, ~uint64_t(0), dst_off, end, nkept, count,
+                                          count},
+                        [&](Scratch& sc) {
+                          return launch_pack<PackPlain>(
+                              c, s,
+                              PackArgs{static_cast<const uint8_t*>(file_base), off,
+                                       reinterpret_cast<const uint64_t*>(sc.d_off_ext), nullptr,
+                                       static_cast<uint8_t*>(dst), dst_bytes, dst_off, count, count, nullptr, nullptr, 0,
+                                       0});
+                        });
+}
+
+int kvsep_vlog_frame_auto_device(kvsep_crc32c_ctx* c, void* stream, const void* base, const uint64_t* seg_off,
+                                 const uint64_t* seg_len, const uint64_t* first, uint32_t* seg_crc, uint32_t* crc_out,
+                                 void* dst, uint64_t dst_bytes, uint64_t start, uint64_t* rec_off, uint64_t* end,
+                                 uint64_t count, uint64_t nseg, uint64_t total_bytes, uint64_t max_len) {
+  int rc = offsets_args("kvsep_vlog_frame_auto_device", nullptr, nullptr, rec_off, end, count);
+  if (rc) return rc;
+  rc = pack_args("kvsep_vlog_frame_auto_device", c, seg_off, seg_len, first, dst, rec_off, count, nseg);
+  if (rc) return rc;
+  if ((nseg && !seg_crc) || (count && !crc_out))
+    return set_err(KVSEP_EINVAL, "kvsep_vlog_frame_auto_device: null seg_crc or crc_out");
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  {  // refused before anything is enqueued
+    DeviceGuard dg(c->device);
+    KVSEP_HIP(dg.err);
+    bool capturing = false;
+    Scratch* psc = nullptr;
+    rc = offsets_scratch(c, s, count, &capturing, &psc);
+    if (rc) return rc;
+  }
+  rc = launch_gather(c, s, base, seg_off, seg_len, first, nullptr, seg_crc, crc_out, count, nseg, total_bytes, max_len);
+  if (rc) return rc;
+  // a payload the header's LE32 length cannot hold is refused as kvsep_vlog_frame_offsets refuses it: no offset for it
+  // or for any record after it, *end = 2^64 - 1
+  rc = launch_offsets(c, s, OffsetsCall{seg_len, first, nullptr, nullptr, 8, 0, start, 0xffffffffull, rec_off, end,
+                                        nullptr, count, nseg});
+  if (rc) return rc;
+  return launch_pack<PackVlog>(c, s,
+                               PackArgs{static_cast<const uint8_t*>(base), seg_off, seg_len, first,
+                                        static_cast<uint8_t*>(dst), dst_bytes, rec_off, count, nseg, crc_out, nullptr, 0,
+                                        0});
+}
 
 int kvsep_sst_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, const uint64_t* off,
                             const uint64_t* len, uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint64_t count,

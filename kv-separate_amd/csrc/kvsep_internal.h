@@ -37,6 +37,9 @@ struct Scratch {
   uint32_t* d_tile_cnt = nullptr;            // list forms: bad blocks per tile of the batch ...
   unsigned long long* d_tile_base = nullptr;  // ... and their exclusive prefix sum (crc32c_verdicts.inc)
   uint64_t cap_tiles = 0;
+  unsigned long long* d_off_ext = nullptr;   // offsets pass: the extent of every block ...
+  unsigned long long* d_off_tile = nullptr;  // ... and per tile [sum | kept | base], then the two grand totals
+  uint64_t cap_off = 0;                      // blocks both are sized for (crc32c_offsets.inc)
   hipEvent_t last_use = nullptr;
   hipStream_t last_stream = nullptr;
   bool used = false;

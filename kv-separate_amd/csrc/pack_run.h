@@ -53,6 +53,9 @@ KVSEP_HD uint64_t add_sat(uint64_t a, uint64_t b) { return a + b < a ? kSaturate
 
 // Whether [dst_off, dst_off + lead + payload + trail) lies inside [0, dst_bytes).  No sum is formed that can wrap; a
 // payload of kSaturated is a sum that did (no buffer holds 2^64 - 1 bytes, so no real block is refused by this).
+// dst_off = 2^64 - 1 is the offsets pass's mark for a block that is not laid out (offsets::kSkip): it is refused for
+// every payload and frame, but for an empty plain block in a destination of 2^64 - 1 bytes, which fits and writes
+// nothing (tests/cpp/offsets_run_test.cc).
 KVSEP_HD bool fits(uint64_t dst_off, uint64_t payload, Frame f, uint64_t dst_bytes) {
   if (dst_off > dst_bytes || payload == kSaturated) return false;
   const uint64_t room = dst_bytes - dst_off, frame = lead(f) + trail(f);

@@ -27,6 +27,7 @@ HEADER_PATH = os.path.join(_HERE, "..", "..", "include", "kvsep_crc32c.h")
 
 KVSEP_OK = 0
 MASK_DELTA = 0xA282EAD8  # util/crc32c.h:22
+OFFSET_SKIP = 2**64 - 1  # KVSEP_OFFSET_SKIP: dst_off of a block the offsets pass did not lay out
 
 _lib = None
 
@@ -108,6 +109,14 @@ _SIGS = {
                                 [ctypes.c_uint64] * 4),
     "kvsep_sst_frame_device": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_uint64, ctypes.c_void_p] +
                                [ctypes.c_uint64] * 3),
+    "kvsep_crc32c_offsets_device": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_uint64] * 3 +
+                                    [ctypes.c_void_p] * 3 + [ctypes.c_uint64] * 2),
+    "kvsep_crc32c_salvage_device": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_uint64] + [ctypes.c_void_p] * 3 +
+                                    [ctypes.c_uint64]),
+    "kvsep_sst_salvage_device": (ctypes.c_int, [ctypes.c_void_p] * 10 + [ctypes.c_uint64] + [ctypes.c_void_p] * 3 +
+                                 [ctypes.c_uint64] * 3),
+    "kvsep_vlog_frame_auto_device": (ctypes.c_int, [ctypes.c_void_p] * 9 + [ctypes.c_uint64] * 2 +
+                                     [ctypes.c_void_p] * 2 + [ctypes.c_uint64] * 4),
     "kvsep_crc32c_group_extend_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                                                       ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]),
     "kvsep_crc32c_batch_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -490,6 +499,59 @@ class Context:
         _check(lib().kvsep_sst_frame_device(self._h, _stream_handle(stream), _dptr(base), _dptr(off), _dptr(length),
                                             _dptr(types), _dptr(masked_out), _dptr(dst), dst_bytes, _dptr(blk_off),
                                             count, total_bytes, max_len), "kvsep_sst_frame_device")
+        return dst
+
+    def offsets_device(self, seg_len, dst_off, end, first=None, keep=None, keep_before=None, head=0, tail=0, start=0,
+                       nkept=None, count=None, nseg=None, stream=None):
+        """kvsep_crc32c_offsets_device: dst_off[i] = start + the (head + size + tail) of the kept blocks before i, or
+        OFFSET_SKIP for a dropped block; end / nkept (one-element uint64 / int64 device tensors) the layout's end and
+        the number of kept blocks.  keep: uint8 device tensor (keep[i] != 0); keep_before: one-element device tensor
+        (i < its value); at most one of them.  Without first, block i is segment i."""
+        nseg = int(seg_len.numel()) if nseg is None else nseg
+        if count is None:
+            count = int(first.numel()) - 1 if first is not None else nseg
+        _check(lib().kvsep_crc32c_offsets_device(self._h, _stream_handle(stream), _dptr(seg_len), _dptr(first),
+                                                 _dptr(keep), _dptr(keep_before), head, tail, start, _dptr(dst_off),
+                                                 _dptr(end), _dptr(nkept), count, nseg),
+               "kvsep_crc32c_offsets_device")
+        return dst_off
+
+    def salvage_device(self, base, off, length, dst, dst_bytes, dst_off, end, keep=None, keep_before=None, nkept=None,
+                       count=None, stream=None):
+        """kvsep_crc32c_salvage_device: the kept blocks of base go back to back to dst from offset 0 (offsets_device,
+        then pack_device with the dst_off it wrote)."""
+        count = int(off.numel()) if count is None else count
+        _check(lib().kvsep_crc32c_salvage_device(self._h, _stream_handle(stream), _dptr(base), _dptr(off),
+                                                 _dptr(length), _dptr(keep), _dptr(keep_before), _dptr(dst), dst_bytes,
+                                                 _dptr(dst_off), _dptr(end), _dptr(nkept), count),
+               "kvsep_crc32c_salvage_device")
+        return dst
+
+    def sst_salvage_device(self, file_base, off, length, out, ok, dst, dst_bytes, dst_off, end, first_bad=None,
+                           nbad=None, nkept=None, count=None, total_bytes=None, max_len=0, stream=None):
+        """kvsep_sst_salvage_device: the SST read check with ok[], then the passed blocks with their 5-byte trailers
+        contiguous in dst; dst_off[i] where block i went (OFFSET_SKIP: it failed)."""
+        count = int(off.numel()) if count is None else count
+        if total_bytes is None:
+            total_bytes = int(length.sum().item()) if count else 0
+        _check(lib().kvsep_sst_salvage_device(self._h, _stream_handle(stream), _dptr(file_base), _dptr(off),
+                                              _dptr(length), _dptr(out), _dptr(first_bad), _dptr(nbad), _dptr(ok),
+                                              _dptr(dst), dst_bytes, _dptr(dst_off), _dptr(end), _dptr(nkept), count,
+                                              total_bytes, max_len), "kvsep_sst_salvage_device")
+        return dst
+
+    def vlog_frame_auto_device(self, base, seg_off, seg_len, first, seg_crc, crc_out, dst, dst_bytes, rec_off, end,
+                               start=0, count=None, nseg=None, total_bytes=None, max_len=0, stream=None):
+        """kvsep_vlog_frame_auto_device: vlog_frame_device with rec_off (an output here) and end computed on the
+        device, records back to back from `start`."""
+        count = int(first.numel()) - 1 if count is None else count
+        nseg = int(seg_len.numel()) if nseg is None else nseg
+        if total_bytes is None:
+            total_bytes = int(seg_len.sum().item()) if nseg else 0
+        _check(lib().kvsep_vlog_frame_auto_device(self._h, _stream_handle(stream), _dptr(base), _dptr(seg_off),
+                                                  _dptr(seg_len), _dptr(first), _dptr(seg_crc), _dptr(crc_out),
+                                                  _dptr(dst), dst_bytes, start, _dptr(rec_off), _dptr(end), count, nseg,
+                                                  total_bytes, max_len), "kvsep_vlog_frame_auto_device")
         return dst
 
     def stream_read(self, src, nbytes: int, sink, stream=None):
