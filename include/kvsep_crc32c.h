@@ -41,7 +41,8 @@ extern "C" {
  * _host, kvsep_crc32c_group_extend_host) came the same way, and so did the device write side
  * (kvsep_crc32c_pack_device, kvsep_vlog_frame_offsets, kvsep_vlog_frame_device, kvsep_sst_frame_device) and the
  * offsets and salvage forms (kvsep_crc32c_offsets_device, kvsep_crc32c_salvage_device, kvsep_sst_salvage_device,
- * kvsep_vlog_frame_auto_device).
+ * kvsep_vlog_frame_auto_device) and the device log / MANIFEST reader (kvsep_log_walk_device,
+ * kvsep_log_accept_gaps_device, kvsep_log_read_device).
  * The reference's C++ symbol leveldb::crc32c::Extend is not in this library: it is in the libkvsep_leveldb_abi.so
  * shim. */
 #define KVSEP_ABI_VERSION 4
@@ -335,6 +336,44 @@ int kvsep_vlog_frame_auto_device(kvsep_crc32c_ctx* ctx, void* stream, const void
                                  const uint64_t* seg_len, const uint64_t* first, uint32_t* seg_crc, uint32_t* crc_out,
                                  void* dst, uint64_t dst_bytes, uint64_t start, uint64_t* rec_off, uint64_t* end,
                                  uint64_t count, uint64_t nseg, uint64_t total_bytes, uint64_t max_len);
+
+/* ---------------------------------------------------------------- log / MANIFEST reader on the device
+ * kvsep_log_walk and kvsep_log_accept_gaps for a log image that is on the device, so that walk -> checksum -> verdict
+ * runs on one stream with no host step and can be captured.  The format is cut into 32 KiB blocks and no physical
+ * record spans two, so a lane walks a block; the record indices come from the offsets pass over the blocks' counts.
+ * ABI 4 gained them as new entry points only.
+ * Every array is a DEVICE pointer; every call is asynchronous on `stream`; results are identical from run to run (no
+ * atomics).  The argument refusals come before any device is touched: a null ctx, a null base with n != 0, a null
+ * required output with cap != 0, a null nrec, cap > 2^32 - 1 -- each KVSEP_EINVAL.
+ * Scratch: a few words per 32 KiB block plus the offsets pass's, sized by kvsep_crc32c_reserve(ctx, count, total_bytes)
+ * with count >= max(cap, ceil(n / 32768)) and total_bytes >= n: a reserved call allocates nothing and can be captured; a
+ * captured call larger than the reservation fails with KVSEP_EINVAL before anything is enqueued.
+ * Memory touched: the image is never written; it is read bytewise at header positions, so every read lies inside
+ * [base, base + n) (and so inside the naturally aligned 16-byte granules that hold a byte of it), whatever the
+ * alignment of base; with n == 0 base is not dereferenced.  Arrays are read and written for exactly the element counts
+ * given below. */
+/* The walk.  *nrec (a device word, required) = what kvsep_log_walk(buf, n, ...) returns for the same bytes.  off / len /
+ * stored / type are each nullable and each written for exactly cap elements: element i < min(*nrec, cap) holds what the
+ * host walk gives for record i, every element from there to cap is 0.  Records past cap are not stored; *nrec > cap
+ * says the arrays were cut (as *nbad > bad_cap does in the list forms).  The padding has len == 0, so the arrays go to
+ * kvsep_log_verify_device(count = cap) as they are: a block of length 0 is never dereferenced there. */
+int kvsep_log_walk_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, uint64_t n, uint64_t* off,
+                          uint64_t* len, uint32_t* stored, uint8_t* type, uint64_t cap, uint64_t* nrec);
+/* The accept rule.  off, len, type and *nrec as the walk above wrote them for the same image (read at indices below
+ * min(*nrec, cap) only); ok has cap bytes.  accept (required) and gap (nullable) are written for exactly cap elements,
+ * 0 at and past min(*nrec, cap); *dropped and *bad_length_bytes are nullable device words.  The outputs equal those of
+ * kvsep_log_accept_gaps(buf, n, ok, count = min(*nrec, cap), ...) byte for byte: *dropped its return value,
+ * *bad_length_bytes its out-parameter. */
+int kvsep_log_accept_gaps_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, uint64_t n,
+                                 const uint64_t* off, const uint64_t* len, const uint8_t* type, const uint8_t* ok,
+                                 const uint64_t* nrec, uint64_t cap, uint8_t* accept, uint8_t* gap, uint64_t* dropped,
+                                 uint64_t* bad_length_bytes);
+/* The whole reader: the walk, kvsep_log_verify_device(count = cap, total_bytes = n, max_len = 32762) and the accept
+ * rule, chained on `stream` with no host step.  off, len, stored, type, ok and accept are required here (cap != 0);
+ * ok[i] at and past the records is 0 (Value("") = 0 and Unmask(0) != 0). */
+int kvsep_log_read_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, uint64_t n, uint64_t* off,
+                          uint64_t* len, uint32_t* stored, uint8_t* type, uint8_t* ok, uint8_t* accept, uint8_t* gap,
+                          uint64_t cap, uint64_t* nrec, uint64_t* dropped, uint64_t* bad_length_bytes);
 
 /* ---------------------------------------------------------------- batched host form
  * Host pointers. Blocks are gathered into pinned staging, copied H2D, checksummed and the

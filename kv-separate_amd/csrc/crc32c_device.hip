@@ -48,6 +48,7 @@
 #include "concat_run.h"
 #include "pack_run.h"
 #include "offsets_run.h"
+#include "log_run.h"
 
 namespace kvsep {
 
@@ -59,6 +60,7 @@ namespace kvsep {
 #include "crc32c_concat.inc"   // crc32c_concat_kernel: the batched combine of the concat and gather forms
 #include "crc32c_pack.inc"     // crc32c_pack_kernel: the byte-exact gather-copy of the pack and frame forms
 #include "crc32c_offsets.inc"  // offsets_*_kernel: the masked offset scan of the offsets and salvage forms
+#include "crc32c_logwalk.inc"  // log_*_kernel: the log / MANIFEST walk and accept rule, a lane per 32 KiB block
 
 }  // namespace kvsep
 
@@ -268,6 +270,22 @@ int ensure_offsets(Scratch& sc, uint64_t count, bool capturing = false) {
   KVSEP_HIP(hipMalloc(&sc.d_off_ext, count * 8));
   KVSEP_HIP(hipMalloc(&sc.d_off_tile, (3 * offsets::tile_count(count) + 2) * 8));
   sc.cap_off = count;
+  return KVSEP_OK;
+}
+
+// The log reader's words (crc32c_logwalk.inc): seven per 32 KiB block of the image, then the stop index.
+constexpr uint64_t kLogWords = 7;
+int ensure_log(Scratch& sc, uint64_t nblocks, bool capturing = false) {
+  if (nblocks <= sc.cap_log && sc.d_log) return KVSEP_OK;
+  if (capturing)
+    return set_err(KVSEP_EINVAL, "a captured log read larger than kvsep_crc32c_reserve sized its capture set for");
+  int rc = quiesce(sc);
+  if (rc) return rc;
+  hipFree(sc.d_log);
+  sc.d_log = nullptr;
+  sc.cap_log = 0;
+  KVSEP_HIP(hipMalloc(&sc.d_log, (kLogWords * nblocks + 1) * 8));
+  sc.cap_log = nblocks;
   return KVSEP_OK;
 }
 
@@ -755,6 +773,7 @@ void free_scratch(Scratch& sc) {
   hipFree(sc.d_tile_base);
   hipFree(sc.d_off_ext);
   hipFree(sc.d_off_tile);
+  hipFree(sc.d_log);
   if (sc.last_use) (void)hipEventDestroy(sc.last_use);
   sc = Scratch();
 }
@@ -883,6 +902,8 @@ int reserve_scratch(kvsep_crc32c_ctx* c, Scratch& sc, uint64_t count, uint64_t t
   rc = ensure_list(sc, count);
   if (rc) return rc;
   rc = ensure_offsets(sc, count);
+  if (rc) return rc;
+  rc = ensure_log(sc, count);
   if (rc) return rc;
   return ensure_plan(sc, count, plan::pieces_reserved(c->piece_bytes, c->piece_auto, c->num_cus, count, total_bytes));
 }
@@ -1446,6 +1467,199 @@ int kvsep_vlog_frame_auto_device(kvsep_crc32c_ctx* c, void* stream, const void* 
                                PackArgs{static_cast<const uint8_t*>(base), seg_off, seg_len, first,
                                         static_cast<uint8_t*>(dst), dst_bytes, rec_off, count, nseg, crc_out, nullptr, 0,
                                         0});
+}
+
+}  // extern "C"
+
+namespace {
+// ---- the log / MANIFEST reader on the device (crc32c_logwalk.inc)
+
+struct LogWalkCall {
+  const void* base;
+  uint64_t n;
+  uint64_t* off;
+  uint64_t* len;
+  uint32_t* stored;
+  uint8_t* type;
+  uint64_t cap;
+  uint64_t* nrec;
+};
+
+struct LogAcceptCall {
+  const void* base;
+  uint64_t n;
+  const uint64_t* off;
+  const uint64_t* len;
+  const uint8_t* type;
+  const uint8_t* ok;
+  const uint64_t* nrec;
+  uint64_t cap;
+  uint8_t* accept;
+  uint8_t* gap;
+  uint64_t* dropped;
+  uint64_t* bad_length;
+};
+
+// Refusals before any device is touched.
+int log_walk_args(const char* who, const kvsep_crc32c_ctx* c, const void* base, uint64_t n, uint64_t cap,
+                  const void* nrec) {
+  const char* what = !c                    ? "null ctx"
+                     : !base && n          ? "null base with n != 0"
+                     : !nrec               ? "null nrec"
+                     : cap > 0xffffffffull ? "cap over 2^32 - 1"
+                                           : nullptr;
+  if (!what) return KVSEP_OK;
+  return set_err(KVSEP_EINVAL, (std::string(who) + ": " + what).c_str());
+}
+
+int log_accept_args(const char* who, const kvsep_crc32c_ctx* c, const LogAcceptCall& a) {
+  int rc = log_walk_args(who, c, a.base, a.n, a.cap, a.nrec);
+  if (rc) return rc;
+  if (a.cap && (!a.off || !a.len || !a.type || !a.ok || !a.accept))
+    return set_err(KVSEP_EINVAL, (std::string(who) + ": null off, len, type, ok or accept with cap != 0").c_str());
+  return KVSEP_OK;
+}
+
+// The scratch of a log call on `s`, checked to hold `nblocks` blocks (and the offsets pass over them when `walk`):
+// refuses a captured call that was not reserved for before anything is enqueued, and allocates for an eager one.
+int log_scratch(kvsep_crc32c_ctx* c, hipStream_t s, uint64_t nblocks, bool walk, bool* capturing, Scratch** psc) {
+  int rc = stream_scratch(c, s, c->sc, capturing, psc);
+  if (rc) return rc;
+  rc = ensure_log(**psc, nblocks, *capturing);
+  if (!rc && walk) rc = ensure_offsets(**psc, nblocks, *capturing);
+  return rc;
+}
+
+// The walk on a scratch the caller has acquired and sized: count, the offsets pass over the counts, fill.
+int launch_log_walk_in(Scratch& sc, hipStream_t s, const LogWalkCall& w) {
+  const uint64_t nb = logrun::block_count(w.n);
+  LogWalkArgs a{};
+  a.img = static_cast<const uint8_t*>(w.base);
+  a.n = w.n, a.nblocks = nb;
+  a.off = w.off, a.len = w.len, a.stored = w.stored, a.type = w.type;
+  a.cap = w.cap;
+  a.nrec = reinterpret_cast<const unsigned long long*>(w.nrec);
+  a.cnt = sc.d_log + 1;
+  a.base = sc.d_log + 1 + nb;
+  if (nb) {
+    log_count_kernel<<<unsigned(logrun::grid_for(nb)), logrun::kThreads, 0, s>>>(a.img, a.n, nb, a.cnt);
+    KVSEP_HIP(hipGetLastError());
+  }
+  // base[b] = the records before block b, *nrec = all of them: block b is "segment" b of cnt[], every block kept
+  int rc = launch_offsets_in(sc, s,
+                             OffsetsCall{reinterpret_cast<const uint64_t*>(a.cnt), nullptr, nullptr, nullptr, 0, 0, 0,
+                                         ~uint64_t(0), reinterpret_cast<uint64_t*>(a.base), w.nrec, nullptr, nb, nb});
+  if (rc) return rc;
+  log_fill_kernel<<<unsigned(logrun::pad_grid(nb, w.cap)), logrun::kThreads, 0, s>>>(a);
+  KVSEP_HIP(hipGetLastError());
+  return KVSEP_OK;
+}
+
+// The accept pass on a scratch the caller has acquired and sized.
+int launch_log_accept_in(Scratch& sc, hipStream_t s, const LogAcceptCall& w) {
+  const uint64_t nb = logrun::block_count(w.n);
+  LogAcceptArgs a{};
+  a.img = static_cast<const uint8_t*>(w.base);
+  a.n = w.n, a.nblocks = nb;
+  a.off = w.off, a.len = w.len, a.type = w.type, a.ok = w.ok;
+  a.nrec = reinterpret_cast<const unsigned long long*>(w.nrec);
+  a.cap = w.cap;
+  a.accept = w.accept, a.gap = w.gap, a.dropped = w.dropped, a.bad_length = w.bad_length;
+  a.stop = sc.d_log;
+  a.first = sc.d_log + 1 + 2 * nb;
+  a.state = sc.d_log + 1 + 3 * nb;
+  a.cand = sc.d_log + 1 + 4 * nb;
+  a.drop = sc.d_log + 1 + 5 * nb;
+  a.badlen = sc.d_log + 1 + 6 * nb;
+  if (nb) {
+    log_block_kernel<<<unsigned(logrun::grid_for(nb)), logrun::kThreads, 0, s>>>(a);
+    KVSEP_HIP(hipGetLastError());
+  }
+  log_stop_kernel<<<1, logrun::kThreads, 0, s>>>(a.cand, nb, a.stop);
+  KVSEP_HIP(hipGetLastError());
+  log_accept_kernel<<<unsigned(logrun::pad_grid(nb, w.cap)), logrun::kThreads, 0, s>>>(a);
+  KVSEP_HIP(hipGetLastError());
+  if (w.dropped || w.bad_length) {
+    log_totals_kernel<<<1, logrun::kThreads, 0, s>>>(a.drop, a.badlen, nb, w.dropped, w.bad_length);
+    KVSEP_HIP(hipGetLastError());
+  }
+  return KVSEP_OK;
+}
+
+// A log call as a call of its own: its scratch is bracketed here.  The caller holds the context's mutex.
+template <typename Body>
+int launch_log(kvsep_crc32c_ctx* c, hipStream_t s, uint64_t n, bool walk, uint64_t verify_count, Body body) {
+  DeviceGuard dg(c->device);
+  KVSEP_HIP(dg.err);
+  bool capturing = false;
+  Scratch* psc = nullptr;
+  int rc = log_scratch(c, s, logrun::block_count(n), walk, &capturing, &psc);
+  if (rc) return rc;
+  Scratch& sc = *psc;
+  if (verify_count) {  // the checksum step's CRC words, refused here rather than between two enqueued steps
+    rc = ensure_sst(sc, verify_count, capturing);
+    if (rc) return rc;
+    const Route r = route_batch(c, verify_count, n, logrun::kBlock - logrun::kTypeAt);
+    if (r.planned) rc = ensure_plan(sc, verify_count, plan::pieces_needed(r.piece_bytes, verify_count, n), capturing);
+    if (rc) return rc;
+  }
+  rc = capturing ? KVSEP_OK : acquire(sc, s);
+  if (rc) return rc;
+  rc = body(sc, capturing);
+  if (rc) {
+    if (!capturing) (void)release(sc, s);
+    return rc;
+  }
+  return capturing ? KVSEP_OK : release(sc, s);
+}
+}  // namespace
+
+extern "C" {
+
+int kvsep_log_walk_device(kvsep_crc32c_ctx* c, void* stream, const void* base, uint64_t n, uint64_t* off,
+                          uint64_t* len, uint32_t* stored, uint8_t* type, uint64_t cap, uint64_t* nrec) {
+  int rc = log_walk_args("kvsep_log_walk_device", c, base, n, cap, nrec);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const LogWalkCall w{base, n, off, len, stored, type, cap, nrec};
+  return launch_log(c, s, n, true, 0, [&](Scratch& sc, bool) { return launch_log_walk_in(sc, s, w); });
+}
+
+int kvsep_log_accept_gaps_device(kvsep_crc32c_ctx* c, void* stream, const void* base, uint64_t n, const uint64_t* off,
+                                 const uint64_t* len, const uint8_t* type, const uint8_t* ok, const uint64_t* nrec,
+                                 uint64_t cap, uint8_t* accept, uint8_t* gap, uint64_t* dropped,
+                                 uint64_t* bad_length_bytes) {
+  const LogAcceptCall w{base, n, off, len, type, ok, nrec, cap, accept, gap, dropped, bad_length_bytes};
+  int rc = log_accept_args("kvsep_log_accept_gaps_device", c, w);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return launch_log(c, s, n, false, 0, [&](Scratch& sc, bool) { return launch_log_accept_in(sc, s, w); });
+}
+
+int kvsep_log_read_device(kvsep_crc32c_ctx* c, void* stream, const void* base, uint64_t n, uint64_t* off,
+                          uint64_t* len, uint32_t* stored, uint8_t* type, uint8_t* ok, uint8_t* accept, uint8_t* gap,
+                          uint64_t cap, uint64_t* nrec, uint64_t* dropped, uint64_t* bad_length_bytes) {
+  const char* who = "kvsep_log_read_device";
+  const LogAcceptCall acc{base, n, off, len, type, ok, nrec, cap, accept, gap, dropped, bad_length_bytes};
+  int rc = log_accept_args(who, c, acc);
+  if (rc) return rc;
+  if (cap && !stored) return set_err(KVSEP_EINVAL, "kvsep_log_read_device: null stored with cap != 0");
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const LogWalkCall w{base, n, off, len, stored, type, cap, nrec};
+  return launch_log(c, s, n, true, cap, [&](Scratch& sc, bool capturing) {
+    int r = launch_log_walk_in(sc, s, w);
+    // the checksum step of kvsep_log_verify_device over all cap elements: the padding has length 0, Value("") = 0 and
+    // Mask(0) != 0 = stored, so ok[] is 0 there
+    if (!r && cap)
+      r = launch_batch_in(c, sc, s, capturing, base, off, len, nullptr, nullptr, sc.d_sst_stored, nullptr, nullptr, cap,
+                          n, logrun::kBlock - logrun::kTypeAt);
+    if (!r) r = launch_list(sc, s, capturing, sc.d_sst_stored, stored, nullptr, ListOut{nullptr, 0, ok}, cap);
+    if (!r) r = launch_log_accept_in(sc, s, acc);
+    return r;
+  });
 }
 
 int kvsep_sst_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, const uint64_t* off,

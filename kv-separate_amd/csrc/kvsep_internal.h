@@ -40,6 +40,8 @@ struct Scratch {
   unsigned long long* d_off_ext = nullptr;   // offsets pass: the extent of every block ...
   unsigned long long* d_off_tile = nullptr;  // ... and per tile [sum | kept | base], then the two grand totals
   uint64_t cap_off = 0;                      // blocks both are sized for (crc32c_offsets.inc)
+  unsigned long long* d_log = nullptr;       // log reader: per 32 KiB block [cnt | base | first | state | cand | drop |
+  uint64_t cap_log = 0;                      // badlen], then the stop word (crc32c_logwalk.inc); blocks it is sized for
   hipEvent_t last_use = nullptr;
   hipStream_t last_stream = nullptr;
   bool used = false;

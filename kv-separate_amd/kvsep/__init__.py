@@ -117,6 +117,12 @@ _SIGS = {
                                  [ctypes.c_uint64] * 3),
     "kvsep_vlog_frame_auto_device": (ctypes.c_int, [ctypes.c_void_p] * 9 + [ctypes.c_uint64] * 2 +
                                      [ctypes.c_void_p] * 2 + [ctypes.c_uint64] * 4),
+    "kvsep_log_walk_device": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 4 +
+                              [ctypes.c_uint64, ctypes.c_void_p]),
+    "kvsep_log_accept_gaps_device": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 5 +
+                                     [ctypes.c_uint64] + [ctypes.c_void_p] * 4),
+    "kvsep_log_read_device": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 7 +
+                              [ctypes.c_uint64] + [ctypes.c_void_p] * 3),
     "kvsep_crc32c_group_extend_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                                                       ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]),
     "kvsep_crc32c_batch_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -437,6 +443,38 @@ class Context:
                                              _dptr(stored), _dptr(ok), count, total_bytes, max_len),
                "kvsep_log_verify_device")
         return ok
+
+    def log_walk_device(self, base, n, nrec, off=None, length=None, stored=None, type=None, cap=None, stream=None):
+        """kvsep_log_walk_device: the walk of log_walk over the n bytes of the device image at base.  nrec (one-element
+        int64 device tensor) receives the number of physical records; off / length (int64), stored (int32) and type
+        (uint8), each optional, are written for exactly cap elements: the records first, zeros after them."""
+        if cap is None:
+            cap = min(int(t.numel()) for t in (off, length, stored, type) if t is not None and not isinstance(t, int))
+        _check(lib().kvsep_log_walk_device(self._h, _stream_handle(stream), _dptr(base), n, _dptr(off), _dptr(length),
+                                           _dptr(stored), _dptr(type), cap, _dptr(nrec)), "kvsep_log_walk_device")
+        return nrec
+
+    def log_accept_gaps_device(self, base, n, off, length, type, ok, nrec, accept, gap=None, dropped=None,
+                               bad_length=None, cap=None, stream=None):
+        """kvsep_log_accept_gaps_device: log_accept_gaps over the device image and the arrays log_walk_device wrote,
+        with the verdicts ok (uint8, cap bytes).  accept / gap (uint8) are written for cap elements; dropped /
+        bad_length are one-element int64 device tensors."""
+        cap = int(ok.numel()) if cap is None else cap
+        _check(lib().kvsep_log_accept_gaps_device(self._h, _stream_handle(stream), _dptr(base), n, _dptr(off),
+                                                  _dptr(length), _dptr(type), _dptr(ok), _dptr(nrec), cap,
+                                                  _dptr(accept), _dptr(gap), _dptr(dropped), _dptr(bad_length)),
+               "kvsep_log_accept_gaps_device")
+        return accept
+
+    def log_read_device(self, base, n, off, length, stored, type, ok, accept, nrec, gap=None, dropped=None,
+                        bad_length=None, cap=None, stream=None):
+        """kvsep_log_read_device: log_walk_device, log_verify_device over all cap elements and log_accept_gaps_device,
+        chained on one stream with no host step."""
+        cap = int(ok.numel()) if cap is None else cap
+        _check(lib().kvsep_log_read_device(self._h, _stream_handle(stream), _dptr(base), n, _dptr(off), _dptr(length),
+                                           _dptr(stored), _dptr(type), _dptr(ok), _dptr(accept), _dptr(gap), cap,
+                                           _dptr(nrec), _dptr(dropped), _dptr(bad_length)), "kvsep_log_read_device")
+        return accept
 
     def concat_device(self, seg_crc, seg_len, first, out, init=None, count=None, nseg=None, stream=None):
         """kvsep_crc32c_concat_device: out[i] = the fold of combine over segments [first[i], first[i + 1]) of seg_crc /
