@@ -42,7 +42,8 @@ extern "C" {
  * (kvsep_crc32c_pack_device, kvsep_vlog_frame_offsets, kvsep_vlog_frame_device, kvsep_sst_frame_device) and the
  * offsets and salvage forms (kvsep_crc32c_offsets_device, kvsep_crc32c_salvage_device, kvsep_sst_salvage_device,
  * kvsep_vlog_frame_auto_device) and the device log / MANIFEST reader (kvsep_log_walk_device,
- * kvsep_log_accept_gaps_device, kvsep_log_read_device).
+ * kvsep_log_accept_gaps_device, kvsep_log_read_device) and its record assembly (kvsep_log_chains,
+ * kvsep_log_chains_device, kvsep_log_records_device).
  * The reference's C++ symbol leveldb::crc32c::Extend is not in this library: it is in the libkvsep_leveldb_abi.so
  * shim. */
 #define KVSEP_ABI_VERSION 4
@@ -116,7 +117,7 @@ int kvsep_crc32c_ctx_set_host_node(kvsep_crc32c_ctx* ctx, int node);
 int kvsep_crc32c_ctx_host_placement(kvsep_crc32c_ctx* ctx, int* device_node, int* staging_node, int* cpus, int cap);
 /* Pre-size scratch so later calls of up to `count` blocks / `total_bytes` bytes do not allocate: the context's own
  * scratch (eager calls) and every free capture set (at least 4 are made).  Required before graph capture; covers the
- * planned, narrow, verify, list, SST-verify, offsets and salvage forms: any batch within both numbers, whatever piece size it picks, and the SST
+ * planned, narrow, verify, list, SST-verify, offsets, salvage, log-read and record-assembly forms: any batch within both numbers, whatever piece size it picks, and the SST
  * read check called with the caller's own total_bytes. */
 int kvsep_crc32c_reserve(kvsep_crc32c_ctx* ctx, uint64_t count, uint64_t total_bytes);
 /* Graph capture (hipStreamBeginCapture ... EndCapture, torch.cuda.graph): every call captured into one graph runs on
@@ -374,6 +375,53 @@ int kvsep_log_accept_gaps_device(kvsep_crc32c_ctx* ctx, void* stream, const void
 int kvsep_log_read_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, uint64_t n, uint64_t* off,
                           uint64_t* len, uint32_t* stored, uint8_t* type, uint8_t* ok, uint8_t* accept, uint8_t* gap,
                           uint64_t cap, uint64_t* nrec, uint64_t* dropped, uint64_t* bad_length_bytes);
+
+/* Record assembly on the device: which physical records join into the logical records log::Reader::ReadRecord returns
+ * (the loop documented at kvsep_log_accept_gaps below).  Consecutive records form a CHAIN: a record that does not
+ * continue the record in progress -- a rejected record, a FULL, a FIRST, a MIDDLE / LAST with gap set or with nothing in
+ * progress, an unknown type -- starts a new one, so the chains cut [0, count) into runs.  A chain is WHOLE, a record the
+ * reader returns, iff it is one accepted FULL or ends with a LAST that continued; its records are then the fragments, in
+ * order.  Every other chain (a lone rejected record, a FIRST cut off by a gap, a MIDDLE with nothing before it, a record
+ * still open at count) is dropped.  first[] / whole[] are the `first` and `keep` of kvsep_crc32c_offsets_device, and
+ * first[] / frag_off[] / frag_len[] the first / seg_off / seg_len of kvsep_crc32c_pack_device and
+ * kvsep_crc32c_gather_device, as they are.  ABI 4 gained these as new entry points only. */
+/* Host, pure, no device: returns the number of chains.  type / accept / gap (nullable: all zero) have count elements;
+ * first has count + 1: first[j] = the first record of chain j, and `count` in every element from nchain to count; whole
+ * has count: whole[j] = 1 for a whole chain, 0 else and at and past nchain; *nwhole (nullable) = the whole chains. */
+uint64_t kvsep_log_chains(const uint8_t* type, const uint8_t* accept, const uint8_t* gap, uint64_t count,
+                          uint64_t* first, uint8_t* whole, uint64_t* nwhole);
+/* The chains pass on the device, asynchronous on `stream`; all pointers are device pointers.  count = min(*nrec, cap);
+ * type / accept / gap (nullable: all zero) / off / len are read at indices below count only.  first (cap + 1 elements),
+ * whole (cap), *nchain (required) and *nwhole (nullable) equal kvsep_log_chains for that count element for element:
+ * first holds `count` from nchain to cap, whole 0 from nchain to cap.  off / len / frag_off / frag_len are all four given
+ * or all four null: frag_off[i] = off[i] + 1 and frag_len[i] = len[i] - 1 for i < count (the walk's off is the type byte,
+ * its len 1 + payload; a len of 0, which no walk gives, yields 0), both 0 from count to cap.  Every array is written for
+ * exactly the stated element count.  Three small kernels ordered by the stream (no atomics) on a few scratch words per
+ * 1,024 records, sized by kvsep_crc32c_reserve(ctx, count >= cap, ...): a reserved call allocates nothing and can be
+ * captured; a captured call larger than the reservation fails with KVSEP_EINVAL before anything is enqueued.  Refused
+ * with KVSEP_EINVAL before any device is touched: a null ctx, a null type / accept / first / whole with cap != 0, some
+ * but not all of off / len / frag_off / frag_len, a null nrec, a null nchain, cap > 2^32 - 1. */
+int kvsep_log_chains_device(kvsep_crc32c_ctx* ctx, void* stream, const uint8_t* type, const uint8_t* accept,
+                            const uint8_t* gap, const uint64_t* off, const uint64_t* len, const uint64_t* nrec,
+                            uint64_t cap, uint64_t* first, uint8_t* whole, uint64_t* frag_off, uint64_t* frag_len,
+                            uint64_t* nchain, uint64_t* nwhole);
+/* The whole reader down to record bytes, chained on `stream` with no host step: kvsep_log_read_device (gap required
+ * here), the chains pass, the offsets pass (seg_len = frag_len, first, keep = whole, head = tail = start = 0, count = nseg
+ * = cap) and the plain gather-copy with the same descriptors.  dst receives the records log::Reader returns, back to
+ * back from offset 0, in order; rec_off[j] (cap words) = where chain j's record went, KVSEP_OFFSET_SKIP for a chain that
+ * is not whole or lies past *nchain; rec_len[j] (nullable, cap words) = the record's byte count when whole[j], else 0;
+ * *end = the bytes needed, *nwhole (nullable) = the records.  The destination contract is kvsep_crc32c_salvage_device's:
+ * a record that does not lie inside [0, dst_bytes) is not written, *end says what was needed, no byte of dst at or past
+ * *end is written.  *nrec > cap says the arrays were cut: the result is then the assembly of the first cap physical
+ * records, a chain open at the cut dropped as at the end of an image; read again with a larger cap.
+ * kvsep_crc32c_reserve(ctx, count >= max(cap, ceil(n / 32768)), total_bytes >= n) makes the call allocation-free and
+ * capturable; a captured call over the reservation is refused before its first kernel. */
+int kvsep_log_records_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, uint64_t n, uint64_t* off,
+                             uint64_t* len, uint32_t* stored, uint8_t* type, uint8_t* ok, uint8_t* accept, uint8_t* gap,
+                             uint64_t cap, uint64_t* nrec, uint64_t* dropped, uint64_t* bad_length_bytes,
+                             uint64_t* frag_off, uint64_t* frag_len, uint64_t* first, uint8_t* whole, uint64_t* nchain,
+                             void* dst, uint64_t dst_bytes, uint64_t* rec_off, uint64_t* rec_len, uint64_t* end,
+                             uint64_t* nwhole);
 
 /* ---------------------------------------------------------------- batched host form
  * Host pointers. Blocks are gathered into pinned staging, copied H2D, checksummed and the

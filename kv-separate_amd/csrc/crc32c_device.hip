@@ -26,7 +26,9 @@
 // One translation unit, in parts: crc32c_fold.inc (the shared device code), crc32c_wide.inc (the wide kernel),
 // crc32c_narrow.inc (the narrow kernels for short blocks), crc32c_support.inc (combine, plan, helpers),
 // crc32c_verdicts.inc (the list pass of the verify forms), crc32c_concat.inc (the batched combine), crc32c_pack.inc
-// (the gather-copy of the pack and frame forms), crc32c_offsets.inc (the offsets pass of the salvage forms), then this file's host side -- the context, kernel routing, launches and the device C ABI.  crc32c_hooks.inc holds the
+// (the gather-copy of the pack and frame forms), crc32c_offsets.inc (the offsets pass of the salvage forms),
+// crc32c_logwalk.inc (the log / MANIFEST walk and accept rule), crc32c_logchain.inc (the chains pass that joins FIRST /
+// MIDDLE / LAST fragments), then this file's host side -- the context, kernel routing, launches and the device C ABI.  crc32c_hooks.inc holds the
 // measurement hook points (empty in the shipped library), crc32c_diag.inc the KVSEP_DIAG build's A/B forms.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -49,6 +51,7 @@
 #include "pack_run.h"
 #include "offsets_run.h"
 #include "log_run.h"
+#include "chain_run.h"
 
 namespace kvsep {
 
@@ -61,6 +64,7 @@ namespace kvsep {
 #include "crc32c_pack.inc"     // crc32c_pack_kernel: the byte-exact gather-copy of the pack and frame forms
 #include "crc32c_offsets.inc"  // offsets_*_kernel: the masked offset scan of the offsets and salvage forms
 #include "crc32c_logwalk.inc"  // log_*_kernel: the log / MANIFEST walk and accept rule, a lane per 32 KiB block
+#include "crc32c_logchain.inc" // chain_*_kernel: the chains pass, FIRST / MIDDLE / LAST fragments into records
 
 }  // namespace kvsep
 
@@ -286,6 +290,22 @@ int ensure_log(Scratch& sc, uint64_t nblocks, bool capturing = false) {
   sc.cap_log = 0;
   KVSEP_HIP(hipMalloc(&sc.d_log, (kLogWords * nblocks + 1) * 8));
   sc.cap_log = nblocks;
+  return KVSEP_OK;
+}
+
+// The chains pass's words (crc32c_logchain.inc): per tile of chain::kTile records a summary and what the scan hands the
+// tile, then the two grand totals.
+int ensure_chain(Scratch& sc, uint64_t cap, bool capturing = false) {
+  if (cap <= sc.cap_chain && sc.d_chain) return KVSEP_OK;
+  if (capturing)
+    return set_err(KVSEP_EINVAL, "a captured chains pass larger than kvsep_crc32c_reserve sized its capture set for");
+  int rc = quiesce(sc);
+  if (rc) return rc;
+  hipFree(sc.d_chain);
+  sc.d_chain = nullptr;
+  sc.cap_chain = 0;
+  KVSEP_HIP(hipMalloc(&sc.d_chain, (2 * chain::tile_count(cap) + 2) * 8));
+  sc.cap_chain = cap;
   return KVSEP_OK;
 }
 
@@ -774,6 +794,7 @@ void free_scratch(Scratch& sc) {
   hipFree(sc.d_off_ext);
   hipFree(sc.d_off_tile);
   hipFree(sc.d_log);
+  hipFree(sc.d_chain);
   if (sc.last_use) (void)hipEventDestroy(sc.last_use);
   sc = Scratch();
 }
@@ -904,6 +925,8 @@ int reserve_scratch(kvsep_crc32c_ctx* c, Scratch& sc, uint64_t count, uint64_t t
   rc = ensure_offsets(sc, count);
   if (rc) return rc;
   rc = ensure_log(sc, count);
+  if (rc) return rc;
+  rc = ensure_chain(sc, count);
   if (rc) return rc;
   return ensure_plan(sc, count, plan::pieces_reserved(c->piece_bytes, c->piece_auto, c->num_cus, count, total_bytes));
 }
@@ -1658,6 +1681,151 @@ int kvsep_log_read_device(kvsep_crc32c_ctx* c, void* stream, const void* base, u
                           n, logrun::kBlock - logrun::kTypeAt);
     if (!r) r = launch_list(sc, s, capturing, sc.d_sst_stored, stored, nullptr, ListOut{nullptr, 0, ok}, cap);
     if (!r) r = launch_log_accept_in(sc, s, acc);
+    return r;
+  });
+}
+
+}  // extern "C"
+
+namespace {
+// ---- the chains pass and the records composite (crc32c_logchain.inc)
+
+struct ChainCall {
+  const uint8_t* type;
+  const uint8_t* accept;
+  const uint8_t* gap;
+  const uint64_t* off;
+  const uint64_t* len;
+  const uint64_t* nrec;
+  uint64_t cap;
+  uint64_t* first;
+  uint8_t* whole;
+  uint64_t* frag_off;
+  uint64_t* frag_len;
+  uint64_t* nchain;
+  uint64_t* nwhole;
+};
+
+// Refusals before any device is touched.
+int chain_args(const char* who, const kvsep_crc32c_ctx* c, const ChainCall& k) {
+  const bool any = k.off || k.len || k.frag_off || k.frag_len, all = k.off && k.len && k.frag_off && k.frag_len;
+  const char* what = !c                                                           ? "null ctx"
+                     : k.cap && (!k.type || !k.accept || !k.first || !k.whole)    ? "null type, accept, first or whole with cap != 0"
+                     : any && !all                                                ? "off, len, frag_off and frag_len go together"
+                     : !k.nrec                                                    ? "null nrec"
+                     : !k.nchain                                                  ? "null nchain"
+                     : k.cap > 0xffffffffull                                      ? "cap over 2^32 - 1"
+                                                                                  : nullptr;
+  if (!what) return KVSEP_OK;
+  return set_err(KVSEP_EINVAL, (std::string(who) + ": " + what).c_str());
+}
+
+// The three kernels on `s`, on a scratch the caller has acquired and sized (ensure_chain).  cap == 0 runs the write
+// kernel alone, which then touches no scratch.
+int launch_chains_in(Scratch& sc, hipStream_t s, const ChainCall& k) {
+  const uint64_t nt = chain::tile_count(k.cap);
+  ChainArgs a{};
+  a.type = k.type, a.accept = k.accept, a.gap = k.gap, a.off = k.off, a.len = k.len;
+  a.nrec = reinterpret_cast<const unsigned long long*>(k.nrec);
+  a.cap = k.cap, a.ntiles = nt;
+  a.first = k.first, a.whole = k.whole, a.frag_off = k.frag_off, a.frag_len = k.frag_len;
+  a.nchain = k.nchain, a.nwhole = k.nwhole;
+  if (nt) {
+    a.sum = sc.d_chain;
+    a.in = sc.d_chain + nt;
+    a.grand = sc.d_chain + 2 * nt;
+    chain_tile_kernel<<<unsigned(nt), chain::kThreads, 0, s>>>(a);
+    KVSEP_HIP(hipGetLastError());
+    chain_scan_kernel<<<1, chain::kScanThreads, 0, s>>>(a.sum, a.in, a.grand, nt);
+    KVSEP_HIP(hipGetLastError());
+  }
+  chain_write_kernel<<<unsigned(chain::write_tiles(k.cap)), chain::kThreads, 0, s>>>(a);
+  KVSEP_HIP(hipGetLastError());
+  return KVSEP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int kvsep_log_chains_device(kvsep_crc32c_ctx* c, void* stream, const uint8_t* type, const uint8_t* accept,
+                            const uint8_t* gap, const uint64_t* off, const uint64_t* len, const uint64_t* nrec,
+                            uint64_t cap, uint64_t* first, uint8_t* whole, uint64_t* frag_off, uint64_t* frag_len,
+                            uint64_t* nchain, uint64_t* nwhole) {
+  const ChainCall k{type, accept, gap, off, len, nrec, cap, first, whole, frag_off, frag_len, nchain, nwhole};
+  int rc = chain_args("kvsep_log_chains_device", c, k);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard dg(c->device);
+  KVSEP_HIP(dg.err);
+  bool capturing = false;
+  Scratch* psc = nullptr;
+  rc = stream_scratch(c, s, c->sc, &capturing, &psc);
+  if (!rc) rc = ensure_chain(*psc, cap, capturing);
+  if (rc) return rc;
+  Scratch& sc = *psc;
+  rc = capturing ? KVSEP_OK : acquire(sc, s);
+  if (rc) return rc;
+  rc = launch_chains_in(sc, s, k);
+  if (rc) {
+    if (!capturing) (void)release(sc, s);
+    return rc;
+  }
+  return capturing ? KVSEP_OK : release(sc, s);
+}
+
+int kvsep_log_records_device(kvsep_crc32c_ctx* c, void* stream, const void* base, uint64_t n, uint64_t* off,
+                             uint64_t* len, uint32_t* stored, uint8_t* type, uint8_t* ok, uint8_t* accept, uint8_t* gap,
+                             uint64_t cap, uint64_t* nrec, uint64_t* dropped, uint64_t* bad_length_bytes,
+                             uint64_t* frag_off, uint64_t* frag_len, uint64_t* first, uint8_t* whole, uint64_t* nchain,
+                             void* dst, uint64_t dst_bytes, uint64_t* rec_off, uint64_t* rec_len, uint64_t* end,
+                             uint64_t* nwhole) {
+  const char* who = "kvsep_log_records_device";
+  const LogAcceptCall acc{base, n, off, len, type, ok, nrec, cap, accept, gap, dropped, bad_length_bytes};
+  int rc = log_accept_args(who, c, acc);
+  if (rc) return rc;
+  if (cap && (!stored || !gap || !frag_off || !frag_len || !dst || !rec_off))
+    return set_err(KVSEP_EINVAL, "kvsep_log_records_device: null stored, gap, frag_off, frag_len, dst or rec_off with cap != 0");
+  if (!end) return set_err(KVSEP_EINVAL, "kvsep_log_records_device: null end");
+  // the assembly state is read from gap[]: the fragment arrays are given whole, so the chains pass writes all four
+  const ChainCall k{type, accept, gap, off, len, nrec, cap, first, whole, frag_off, frag_len, nchain, nullptr};
+  rc = chain_args(who, c, k);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  {  // the chains pass and the layout over cap chains: refused before anything is enqueued
+    DeviceGuard dg(c->device);
+    KVSEP_HIP(dg.err);
+    bool capturing = false;
+    Scratch* psc = nullptr;
+    rc = offsets_scratch(c, s, cap, &capturing, &psc);
+    if (!rc) rc = ensure_chain(*psc, cap, capturing);
+    if (rc) return rc;
+  }
+  const LogWalkCall w{base, n, off, len, stored, type, cap, nrec};
+  return launch_log(c, s, n, true, cap, [&](Scratch& sc, bool capturing) {
+    int r = launch_log_walk_in(sc, s, w);
+    if (!r && cap)
+      r = launch_batch_in(c, sc, s, capturing, base, off, len, nullptr, nullptr, sc.d_sst_stored, nullptr, nullptr, cap,
+                          n, logrun::kBlock - logrun::kTypeAt);
+    if (!r) r = launch_list(sc, s, capturing, sc.d_sst_stored, stored, nullptr, ListOut{nullptr, 0, ok}, cap);
+    if (!r) r = launch_log_accept_in(sc, s, acc);
+    if (!r) r = launch_chains_in(sc, s, k);
+    // The layout: chain j is the fragments [first[j], first[j + 1]), kept when whole.  The walk's offsets pass is done
+    // with the pass's scratch by now: its result went to the log words, which the fill kernel has read.
+    if (!r)
+      r = launch_offsets_in(sc, s, OffsetsCall{frag_len, first, whole, nullptr, 0, 0, 0, ~uint64_t(0), rec_off, end,
+                                               nwhole, cap, cap});
+    if (!r && rec_len && cap) {
+      chain_reclen_kernel<<<unsigned((cap + chain::kThreads - 1) / chain::kThreads), chain::kThreads, 0, s>>>(
+          sc.d_off_ext, rec_len, cap);
+      if (hipGetLastError() != hipSuccess) r = set_err(KVSEP_EHIP, "chain_reclen_kernel launch");
+    }
+    if (!r)
+      r = launch_pack<PackPlain>(c, s,
+                                 PackArgs{static_cast<const uint8_t*>(base), frag_off, frag_len, first,
+                                          static_cast<uint8_t*>(dst), dst_bytes, rec_off, cap, cap, nullptr, nullptr, 0,
+                                          0});
     return r;
   });
 }

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/kvsep_crc32c.h"
+#include "chain_run.h"
 
 namespace kvsep {
 // crc32c_host.cpp: copies dst[i] <- src[i] (n[i] bytes) on the context's copier threads.
@@ -373,6 +374,30 @@ uint64_t kvsep_log_accept_gaps(const char* buf, uint64_t n, const uint8_t* ok, u
       });
   if (bad_length_bytes) *bad_length_bytes = bad_length;
   return dropped;
+}
+
+uint64_t kvsep_log_chains(const uint8_t* type, const uint8_t* accept, const uint8_t* gap, uint64_t count,
+                          uint64_t* first, uint8_t* whole, uint64_t* nwhole) {
+  namespace chain = kvsep::chain;
+  const auto gap_at = [&](uint64_t i) { return gap ? gap[i] : uint8_t(0); };
+  uint64_t nchain = 0, nw = 0;
+  bool in = false;  // a record is in progress (chain_run.h holds every rule)
+  for (uint64_t i = 0; i < count; ++i) {
+    const bool joins = chain::continues(type[i], accept[i], gap_at(i), in);
+    if (!joins) first[nchain++] = i;
+    in = chain::apply(in, chain::op_of(type[i], accept[i], gap_at(i)));
+    const uint64_t nx = chain::next_index(i, count);
+    if (chain::chain_ends(i, count, chain::continues(type[nx], accept[nx], gap_at(nx), in))) {
+      whole[nchain - 1] = chain::whole_end(type[i], accept[i], joins) ? 1 : 0;
+      nw += whole[nchain - 1];
+    }
+  }
+  for (uint64_t k = nchain; k <= count; ++k) {
+    if (chain::pads_first(k, nchain, count)) first[k] = chain::pad_first(count);
+    if (chain::pads_whole(k, nchain, count)) whole[k] = 0;
+  }
+  if (nwhole) *nwhole = nw;
+  return nchain;
 }
 
 }  // extern "C"

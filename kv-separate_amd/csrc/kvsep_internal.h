@@ -42,6 +42,8 @@ struct Scratch {
   uint64_t cap_off = 0;                      // blocks both are sized for (crc32c_offsets.inc)
   unsigned long long* d_log = nullptr;       // log reader: per 32 KiB block [cnt | base | first | state | cand | drop |
   uint64_t cap_log = 0;                      // badlen], then the stop word (crc32c_logwalk.inc); blocks it is sized for
+  unsigned long long* d_chain = nullptr;     // chains pass: per tile of records [summary | incoming state and base], then
+  uint64_t cap_chain = 0;                    // the two grand totals (crc32c_logchain.inc); records it is sized for
   hipEvent_t last_use = nullptr;
   hipStream_t last_stream = nullptr;
   bool used = false;

@@ -123,6 +123,11 @@ _SIGS = {
                                      [ctypes.c_uint64] + [ctypes.c_void_p] * 4),
     "kvsep_log_read_device": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 7 +
                               [ctypes.c_uint64] + [ctypes.c_void_p] * 3),
+    "kvsep_log_chains": (ctypes.c_uint64, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 3),
+    "kvsep_log_chains_device": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_uint64] + [ctypes.c_void_p] * 6),
+    "kvsep_log_records_device": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 7 +
+                                 [ctypes.c_uint64] + [ctypes.c_void_p] * 9 + [ctypes.c_uint64] +
+                                 [ctypes.c_void_p] * 4),
     "kvsep_crc32c_group_extend_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                                                       ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]),
     "kvsep_crc32c_batch_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -475,6 +480,34 @@ class Context:
                                            _dptr(stored), _dptr(type), _dptr(ok), _dptr(accept), _dptr(gap), cap,
                                            _dptr(nrec), _dptr(dropped), _dptr(bad_length)), "kvsep_log_read_device")
         return accept
+
+    def log_chains_device(self, type, accept, nrec, first, whole, nchain, gap=None, off=None, length=None,
+                          frag_off=None, frag_len=None, nwhole=None, cap=None, stream=None):
+        """kvsep_log_chains_device: log_chains over the arrays the device reader wrote, count = min(nrec, cap).  first
+        (int64, cap + 1 elements) and whole (uint8, cap) are written in full; off / length / frag_off / frag_len
+        (int64, cap) go together: frag_* receive the records' payload descriptors.  nrec, nchain and nwhole are
+        one-element int64 device tensors."""
+        cap = int(whole.numel()) if cap is None else cap
+        _check(lib().kvsep_log_chains_device(self._h, _stream_handle(stream), _dptr(type), _dptr(accept), _dptr(gap),
+                                             _dptr(off), _dptr(length), _dptr(nrec), cap, _dptr(first), _dptr(whole),
+                                             _dptr(frag_off), _dptr(frag_len), _dptr(nchain), _dptr(nwhole)),
+               "kvsep_log_chains_device")
+        return first, whole
+
+    def log_records_device(self, base, n, off, length, stored, type, ok, accept, gap, nrec, frag_off, frag_len, first,
+                           whole, nchain, dst, dst_bytes, rec_off, end, rec_len=None, nwhole=None, dropped=None,
+                           bad_length=None, cap=None, stream=None):
+        """kvsep_log_records_device: log_read_device, log_chains_device, the offsets pass over the chains (keep = whole)
+        and the gather-copy, chained on one stream with no host step: dst receives the records log::Reader returns, back
+        to back from offset 0; rec_off / rec_len (int64, cap) say where each chain's record went and how long it is."""
+        cap = int(ok.numel()) if cap is None else cap
+        _check(lib().kvsep_log_records_device(self._h, _stream_handle(stream), _dptr(base), n, _dptr(off),
+                                              _dptr(length), _dptr(stored), _dptr(type), _dptr(ok), _dptr(accept),
+                                              _dptr(gap), cap, _dptr(nrec), _dptr(dropped), _dptr(bad_length),
+                                              _dptr(frag_off), _dptr(frag_len), _dptr(first), _dptr(whole),
+                                              _dptr(nchain), _dptr(dst), dst_bytes, _dptr(rec_off), _dptr(rec_len),
+                                              _dptr(end), _dptr(nwhole)), "kvsep_log_records_device")
+        return dst
 
     def concat_device(self, seg_crc, seg_len, first, out, init=None, count=None, nseg=None, stream=None):
         """kvsep_crc32c_concat_device: out[i] = the fold of combine over segments [first[i], first[i + 1]) of seg_crc /
@@ -883,6 +916,26 @@ def log_accept_gaps(image, ok):
                                           acc.ctypes.data_as(ctypes.c_void_p), gap.ctypes.data_as(ctypes.c_void_p),
                                           ctypes.byref(bad_len))
     return acc[:ok.size], gap[:ok.size], int(dropped), int(bad_len.value)
+
+
+def log_chains(type, accept, gap=None):
+    """kvsep_log_chains: the chains of the physical records (type from log_walk, accept / gap from log_accept_gaps) ->
+    (first, whole, nchain, nwhole).  first has count + 1 entries: chain j is the records [first[j], first[j + 1]), and
+    first[nchain:] = count; whole[j] = 1 where chain j is a record log::Reader returns."""
+    type = np.ascontiguousarray(type, dtype=np.uint8)
+    accept = np.ascontiguousarray(accept, dtype=np.uint8)
+    count = type.size
+    if accept.size != count or (gap is not None and np.size(gap) != count):
+        raise ValueError("type, accept and gap must have one element per record")
+    vp = ctypes.c_void_p
+    g = None if gap is None else np.ascontiguousarray(gap, dtype=np.uint8)
+    first = np.zeros(count + 1, np.uint64)
+    whole = np.zeros(max(count, 1), np.uint8)
+    nwhole = ctypes.c_uint64()
+    nchain = lib().kvsep_log_chains(type.ctypes.data_as(vp), accept.ctypes.data_as(vp),
+                                    None if g is None else g.ctypes.data_as(vp), count, first.ctypes.data_as(vp),
+                                    whole.ctypes.data_as(vp), ctypes.byref(nwhole))
+    return first, whole[:count], int(nchain), int(nwhole.value)
 
 
 def partition(length, parts: int) -> np.ndarray:
