@@ -43,7 +43,8 @@ extern "C" {
  * offsets and salvage forms (kvsep_crc32c_offsets_device, kvsep_crc32c_salvage_device, kvsep_sst_salvage_device,
  * kvsep_vlog_frame_auto_device) and the device log / MANIFEST reader (kvsep_log_walk_device,
  * kvsep_log_accept_gaps_device, kvsep_log_read_device) and its record assembly (kvsep_log_chains,
- * kvsep_log_chains_device, kvsep_log_records_device).
+ * kvsep_log_chains_device, kvsep_log_records_device) and the device log / MANIFEST writer (kvsep_log_frame_layout,
+ * kvsep_log_frame_device).
  * The reference's C++ symbol leveldb::crc32c::Extend is not in this library: it is in the libkvsep_leveldb_abi.so
  * shim. */
 #define KVSEP_ABI_VERSION 4
@@ -470,6 +471,48 @@ int kvsep_log_verify_device(kvsep_crc32c_ctx* ctx, void* stream, const void* bas
  * call.  dst receives the appended bytes; *written = their count (also on KVSEP_EINVAL for a short dst). */
 int kvsep_log_frame_host(kvsep_crc32c_ctx* ctx, const char* const* payload, const uint64_t* len, uint64_t count,
                          uint64_t dest_length, char* dst, uint64_t dst_cap, uint64_t* written);
+/* Where that writer puts `count` records of len[i] bytes appended to a log of dest_length bytes.  Host, pure, no device.
+ * keep (nullable: every record kept) drops record i when keep[i] == 0: it is not written and changes nothing.
+ *   rec_at[i]     (count)     = the offset of record i's first header, relative to the first appended byte;
+ *                               KVSEP_OFFSET_SKIP for a dropped record,
+ *   frag_first[i] (count + 1) = the physical records (fragments) of the records before i; frag_first[count] = *nfrag,
+ *   *written                  = the appended bytes (what kvsep_log_frame_host reports for the kept records).
+ * The zero trailer of a block with fewer than 7 bytes left belongs to the NEXT kept record, as in the writer: none
+ * follows the last record, and dest_length % 32768 > 32761 puts one in front of the first.  A kept empty record is one
+ * 7-byte FULL header.  *nfrag <= 2 * kept + total_bytes / 32761 (a record has one fragment, one more for the block it
+ * starts in when it does not fit, and one per further 32,761 bytes), which sizes frag_cap and, with *written, dst.
+ * Sums saturate at 2^64 - 1 as in kvsep_crc32c_offsets_device: a kept record whose end saturates, and every kept record
+ * after it, gets KVSEP_OFFSET_SKIP and owns no fragment, and *written = 2^64 - 1.  Returns KVSEP_EINVAL for a null
+ * frag_first, or a null len / rec_at with count != 0; nfrag and written are nullable.  ABI 4 gained this and
+ * kvsep_log_frame_device as new entry points only. */
+int kvsep_log_frame_layout(const uint64_t* len, const uint8_t* keep, uint64_t count, uint64_t dest_length,
+                           uint64_t* rec_at, uint64_t* frag_first, uint64_t* nfrag, uint64_t* written);
+/* The write side on the device, asynchronous on `stream`; every array is a device pointer.  Record i is the bytes
+ * [base + off[i], + len[i]); a dropped record (keep[i] == 0; keep nullable) is never dereferenced whatever its off, so
+ * rec_off / rec_len / whole of kvsep_log_records_device go in as off / len / keep with count = cap.  Lengths are trusted
+ * as in kvsep_crc32c_batch_device.  dst[0, dst_bytes) receives the appended bytes from offset 0: headers, fragments and
+ * zero trailers, byte for byte what kvsep_log_frame_host writes for the kept records.  rec_at (count), frag_first
+ * (count + 1), *nfrag and *written (all three required) equal kvsep_log_frame_layout.  Per fragment slot f < frag_cap,
+ * each array written for exactly frag_cap elements:
+ *   frag_off[f] / frag_len[f] = the fragment's bytes (an offset from base; at most 32,761 bytes),
+ *   frag_at[f]   = its header's offset in dst,   frag_type[f] = 1 FULL, 2 FIRST, 3 MIDDLE, 4 LAST,
+ *   frag_crc[f]  = Extend(Value(&type, 1), fragment), unmasked (the header stores Mask of it),
+ * and 0 / 0 / KVSEP_OFFSET_SKIP / 0 / 0 at and past min(*nfrag, frag_cap).  *nfrag > frag_cap says the fragment arrays
+ * were cut: fragments at or past frag_cap are not written to dst, nor is the zero trailer in front of a record whose
+ * first fragment is; call again with a larger cap.  A fragment (header and bytes) that does not lie inside
+ * [0, dst_bytes) is not written at all, and neither is a trailer; *written says what was needed, and no byte of dst at
+ * or past *written is written.  total_bytes is the hint of the checksum pass (the kept bytes).
+ * Two small kernels (the layout: one wavefront, 64 records a step; the fragment fill), the batched checksum with
+ * max_len 32,761 and the gather-copy with the log frame, ordered by the stream, no atomics; scratch is one word per
+ * record and per fragment slot.  kvsep_crc32c_reserve(ctx, count >= max(count, frag_cap), total_bytes) makes the call
+ * allocation-free and capturable; a captured call over the reservation is refused before its first kernel.  Refused with
+ * KVSEP_EINVAL before any device is touched: a null ctx; a null base / off / len / rec_at with count != 0; a null
+ * fragment array or dst with frag_cap != 0; a null frag_first, nfrag or written; count or frag_cap over 2^32 - 1. */
+int kvsep_log_frame_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, const uint64_t* off,
+                           const uint64_t* len, const uint8_t* keep, uint64_t count, uint64_t dest_length, void* dst,
+                           uint64_t dst_bytes, uint64_t* rec_at, uint64_t* frag_first, uint64_t* frag_off,
+                           uint64_t* frag_len, uint64_t* frag_at, uint8_t* frag_type, uint32_t* frag_crc,
+                           uint64_t frag_cap, uint64_t* nfrag, uint64_t* written, uint64_t total_bytes);
 /* What log::Reader::ReadPhysicalRecord returns, given the walk (off as from kvsep_log_walk) and each record's
  * checksum verdict ok[i]: a mismatch drops the rest of its 32 KiB block buffer (db/log_reader.cc:250-258), so
  * that record and every later record of the same block get accept[i] = 0.  Returns the bytes reported as

@@ -52,6 +52,7 @@
 #include "offsets_run.h"
 #include "log_run.h"
 #include "chain_run.h"
+#include "logw_run.h"
 
 namespace kvsep {
 
@@ -65,6 +66,7 @@ namespace kvsep {
 #include "crc32c_offsets.inc"  // offsets_*_kernel: the masked offset scan of the offsets and salvage forms
 #include "crc32c_logwalk.inc"  // log_*_kernel: the log / MANIFEST walk and accept rule, a lane per 32 KiB block
 #include "crc32c_logchain.inc" // chain_*_kernel: the chains pass, FIRST / MIDDLE / LAST fragments into records
+#include "crc32c_logframe.inc" // logw_*_kernel: the log / MANIFEST write side, records into fragments and pads
 
 }  // namespace kvsep
 
@@ -306,6 +308,25 @@ int ensure_chain(Scratch& sc, uint64_t cap, bool capturing = false) {
   sc.cap_chain = 0;
   KVSEP_HIP(hipMalloc(&sc.d_chain, (2 * chain::tile_count(cap) + 2) * 8));
   sc.cap_chain = cap;
+  return KVSEP_OK;
+}
+
+// The log write side's words (crc32c_logframe.inc): one per record (its block offset and pad count) and one per fragment
+// slot (the init of its checksum).
+int ensure_logw(Scratch& sc, uint64_t n, bool capturing = false) {
+  if (n <= sc.cap_logw && sc.d_logw_rec) return KVSEP_OK;
+  if (capturing)
+    return set_err(KVSEP_EINVAL, "a captured log frame larger than kvsep_crc32c_reserve sized its capture set for");
+  int rc = quiesce(sc);
+  if (rc) return rc;
+  hipFree(sc.d_logw_rec);
+  hipFree(sc.d_logw_seed);
+  sc.d_logw_rec = nullptr;
+  sc.d_logw_seed = nullptr;
+  sc.cap_logw = 0;
+  KVSEP_HIP(hipMalloc(&sc.d_logw_rec, (n ? n : 1) * 4));
+  KVSEP_HIP(hipMalloc(&sc.d_logw_seed, (n ? n : 1) * 4));
+  sc.cap_logw = n;
   return KVSEP_OK;
 }
 
@@ -795,6 +816,8 @@ void free_scratch(Scratch& sc) {
   hipFree(sc.d_off_tile);
   hipFree(sc.d_log);
   hipFree(sc.d_chain);
+  hipFree(sc.d_logw_rec);
+  hipFree(sc.d_logw_seed);
   if (sc.last_use) (void)hipEventDestroy(sc.last_use);
   sc = Scratch();
 }
@@ -927,6 +950,8 @@ int reserve_scratch(kvsep_crc32c_ctx* c, Scratch& sc, uint64_t count, uint64_t t
   rc = ensure_log(sc, count);
   if (rc) return rc;
   rc = ensure_chain(sc, count);
+  if (rc) return rc;
+  rc = ensure_logw(sc, count);
   if (rc) return rc;
   return ensure_plan(sc, count, plan::pieces_reserved(c->piece_bytes, c->piece_auto, c->num_cus, count, total_bytes));
 }
@@ -1828,6 +1853,87 @@ int kvsep_log_records_device(kvsep_crc32c_ctx* c, void* stream, const void* base
                                           0});
     return r;
   });
+}
+
+// ---- the log / MANIFEST write side (crc32c_logframe.inc)
+int kvsep_log_frame_device(kvsep_crc32c_ctx* c, void* stream, const void* base, const uint64_t* off,
+                           const uint64_t* len, const uint8_t* keep, uint64_t count, uint64_t dest_length, void* dst,
+                           uint64_t dst_bytes, uint64_t* rec_at, uint64_t* frag_first, uint64_t* frag_off,
+                           uint64_t* frag_len, uint64_t* frag_at, uint8_t* frag_type, uint32_t* frag_crc,
+                           uint64_t frag_cap, uint64_t* nfrag, uint64_t* written, uint64_t total_bytes) {
+  const char* what =
+      !c                                                                             ? "null ctx"
+      : count && (!base || !off || !len || !rec_at)                                  ? "null base, off, len or rec_at with count != 0"
+      : frag_cap && (!frag_off || !frag_len || !frag_at || !frag_type || !frag_crc || !dst)
+          ? "null fragment array or dst with frag_cap != 0"
+      : !frag_first || !nfrag || !written                                            ? "null frag_first, nfrag or written"
+      : count > 0xffffffffull || frag_cap > 0xffffffffull                            ? "count or frag_cap over 2^32 - 1"
+                                                                                     : nullptr;
+  if (what) return set_err(KVSEP_EINVAL, (std::string("kvsep_log_frame_device: ") + what).c_str());
+  // Value(&type, 1) for FULL .. LAST (log_writer.cc:16-21), once
+  static const struct Seeds {
+    uint32_t v[5];
+    Seeds() {
+      for (int t = 0; t < 5; ++t) {
+        const char ch = char(t);
+        v[t] = kvsep_crc32c_extend_host(0, &ch, 1);
+      }
+    }
+  } seeds;
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard dg(c->device);
+  KVSEP_HIP(dg.err);
+  // every scratch size is checked before the first kernel: the two words of this pass, and the plan of the checksum
+  // call when the context's piece size puts 32,761-byte fragments through one
+  bool capturing = false;
+  Scratch* psc = nullptr;
+  int rc = stream_scratch(c, s, c->sc, &capturing, &psc);
+  if (!rc) rc = ensure_logw(*psc, logw::fill_lanes(count, frag_cap), capturing);
+  if (rc) return rc;
+  Scratch& sc = *psc;
+  if (frag_cap) {
+    const Route r = route_batch(c, frag_cap, total_bytes, logw::kAvail);
+    if (r.planned) rc = ensure_plan(sc, frag_cap, plan::pieces_needed(r.piece_bytes, frag_cap, total_bytes), capturing);
+    if (rc) return rc;
+  }
+  rc = capturing ? KVSEP_OK : acquire(sc, s);
+  if (rc) return rc;
+  LogwArgs a{};
+  a.off = off, a.len = len, a.keep = keep, a.count = count;
+  a.b0 = logw::start_state(dest_length);
+  a.dst = static_cast<uint8_t*>(dst), a.dst_bytes = dst_bytes;
+  a.rec_at = rec_at, a.frag_first = frag_first;
+  a.frag_off = frag_off, a.frag_len = frag_len, a.frag_at = frag_at, a.frag_type = frag_type, a.frag_cap = frag_cap;
+  a.nfrag = nfrag, a.written = written;
+  a.rec = sc.d_logw_rec, a.seed = sc.d_logw_seed;
+  a.s1 = seeds.v[logw::kFull], a.s2 = seeds.v[logw::kFirst], a.s3 = seeds.v[logw::kMiddle], a.s4 = seeds.v[logw::kLast];
+  const auto body = [&]() -> int {
+    logw_layout_kernel<<<1, logw::kLayoutThreads, 0, s>>>(a);
+    KVSEP_HIP(hipGetLastError());
+    const uint64_t lanes = logw::fill_lanes(count, frag_cap);
+    if (lanes) {
+      logw_fill_kernel<<<unsigned((lanes + logw::kFillThreads - 1) / logw::kFillThreads), logw::kFillThreads, 0, s>>>(a);
+      KVSEP_HIP(hipGetLastError());
+    }
+    if (!frag_cap) return KVSEP_OK;
+    // the fragments' checksums: the batched form over all frag_cap slots, the seeds as init (a padding slot has length
+    // 0 and seed 0: frag_crc = 0 there), then the copy that stamps each header in front of its fragment
+    int r = launch_batch_in(c, sc, s, capturing, base, frag_off, frag_len, sc.d_logw_seed, nullptr, frag_crc, nullptr,
+                            nullptr, frag_cap, total_bytes, logw::kAvail);
+    if (r) return r;
+    // fragment f is segment f: no first[]; a padding slot's kSkip lies in no destination (pack::fits)
+    return launch_pack<PackLog>(c, s,
+                                PackArgs{static_cast<const uint8_t*>(base), frag_off, frag_len, nullptr,
+                                         static_cast<uint8_t*>(dst), dst_bytes, frag_at, frag_cap, frag_cap, frag_crc,
+                                         frag_type, 0, 0});
+  };
+  rc = body();
+  if (rc) {
+    if (!capturing) (void)release(sc, s);
+    return rc;
+  }
+  return capturing ? KVSEP_OK : release(sc, s);
 }
 
 int kvsep_sst_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, const uint64_t* off,

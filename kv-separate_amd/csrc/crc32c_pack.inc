@@ -5,6 +5,7 @@
 //   PackPlain  nothing                                                        (kvsep_crc32c_pack_device)
 //   PackVlog   [Mask(crc[i]) LE32][len_i LE32] in front, lead = 8             (db/value_log_writer.cc:46-76)
 //   PackSst    [types[i]][crc[i] LE32] behind, crc[i] the masked trailer word (table/table_builder.cc:209-232)
+//   PackLog    [Mask(crc[i]) LE32][len_i LE16][types[i]] in front, lead = 7      (db/log_writer.cc:84-115)
 // A framed block that does not lie inside [0, dst_bytes) is not written at all.
 //
 // Every index and byte decision comes from pack_run.h, which tests/cpp/pack_run_test.cc runs lane by lane on the CPU.
@@ -38,6 +39,9 @@ struct PackVlog {
 struct PackSst {
   static constexpr pack::Frame kFrame = pack::kSst;
 };
+struct PackLog {
+  static constexpr pack::Frame kFrame = pack::kLog;
+};
 
 struct PackArgs {
   const uint8_t* base;
@@ -48,8 +52,8 @@ struct PackArgs {
   uint64_t dst_bytes;
   const uint64_t* dst_off;
   uint64_t count, nseg;
-  const uint32_t* crc;   // PackVlog: Value(payload i), masked here; PackSst: the trailer word as it is stored
-  const uint8_t* types;  // PackSst
+  const uint32_t* crc;   // PackVlog / PackLog: the CRC, masked here; PackSst: the trailer word as it is stored
+  const uint8_t* types;  // PackSst, PackLog
   uint32_t short_wgs;    // workgroups of the first part of the grid
   uint32_t team;         // workgroups per chunk in the second
 };
@@ -175,6 +179,11 @@ __global__ void __launch_bounds__(kPackThreads) crc32c_pack_kernel(PackArgs a) {
           const uint32_t word = a.crc[b0 + uint32_t(src)];
           const uint8_t type = a.types[b0 + uint32_t(src)];
           if (lane < 5) pack_st8(rec + tot + lane, pack::sst_trailer_byte(type, word, lane));
+        }
+        if constexpr (F::kFrame == pack::kLog) {
+          const uint32_t masked = mask_crc(a.crc[b0 + uint32_t(src)]);
+          const uint8_t type = a.types[b0 + uint32_t(src)];
+          if (lane < 7) pack_st8(rec + lane, pack::log_header_byte(masked, tot, type, lane));
         }
       }
       pack_tile(a, run, tot, at + pack::lead(F::kFrame), t, lane);

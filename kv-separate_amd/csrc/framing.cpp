@@ -17,6 +17,7 @@
 
 #include "../../include/kvsep_crc32c.h"
 #include "chain_run.h"
+#include "logw_run.h"
 
 namespace kvsep {
 // crc32c_host.cpp: copies dst[i] <- src[i] (n[i] bytes) on the context's copier threads.
@@ -271,6 +272,30 @@ int kvsep_log_frame_host(kvsep_crc32c_ctx* ctx, const char* const* payload, cons
     h[5] = char(frags[i].len >> 8);
     h[6] = char(frags[i].type);
   }
+  return KVSEP_OK;
+}
+
+int kvsep_log_frame_layout(const uint64_t* len, const uint8_t* keep, uint64_t count, uint64_t dest_length,
+                           uint64_t* rec_at, uint64_t* frag_first, uint64_t* nfrag, uint64_t* written) {
+  namespace logw = kvsep::logw;
+  if (!frag_first || (count && (!len || !rec_at))) return einval("kvsep_log_frame_layout: null argument");
+  const uint32_t b0 = logw::start_state(dest_length);
+  uint32_t raw = b0;               // the writer's offset behind the records so far (logw_run.h holds every rule)
+  uint64_t block = 0, total = 0;   // blocks advanced, fragments
+  for (uint64_t i = 0; i < count; ++i) {
+    const bool kept = !keep || keep[i] != 0;
+    frag_first[i] = total;
+    const uint32_t b = logw::start_of(raw);
+    const uint64_t nf = kept ? logw::nfrag(b, len[i]) : 0;
+    block = logw::add_sat(block, kept ? logw::blocks_advanced(logw::resets(raw), nf) : 0);
+    raw = logw::raw_behind(raw, kept, logw::step_of(kept, len[i]));
+    const bool is_laid = logw::laid(kept, block, raw);
+    rec_at[i] = logw::rec_at(is_laid, block, nf, b, b0);
+    total = logw::add_sat(total, logw::frags_of(is_laid, nf));
+  }
+  frag_first[count] = total;
+  if (nfrag) *nfrag = total;
+  if (written) *written = logw::rel(logw::pos_sat(block, raw), b0);
   return KVSEP_OK;
 }
 

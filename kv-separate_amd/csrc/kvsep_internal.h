@@ -44,6 +44,9 @@ struct Scratch {
   uint64_t cap_log = 0;                      // badlen], then the stop word (crc32c_logwalk.inc); blocks it is sized for
   unsigned long long* d_chain = nullptr;     // chains pass: per tile of records [summary | incoming state and base], then
   uint64_t cap_chain = 0;                    // the two grand totals (crc32c_logchain.inc); records it is sized for
+  uint32_t* d_logw_rec = nullptr;            // log write side: a word per record ...
+  uint32_t* d_logw_seed = nullptr;           // ... and per fragment slot (crc32c_logframe.inc)
+  uint64_t cap_logw = 0;                     // records / fragment slots both are sized for
   hipEvent_t last_use = nullptr;
   hipStream_t last_stream = nullptr;
   bool used = false;

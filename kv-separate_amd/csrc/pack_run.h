@@ -42,9 +42,9 @@ constexpr uint32_t kChunkBlocks = 64;
 constexpr uint32_t kMinTeam = 4;
 
 // Frame bytes before and after the payload: vlog records carry [Mask(crc) LE32][len LE32] in front, SST blocks
-// [type][Mask(crc) LE32] behind.
-enum Frame : uint32_t { kPlain = 0, kVlog = 1, kSst = 2 };
-KVSEP_HD uint64_t lead(Frame f) { return f == kVlog ? 8 : 0; }
+// [type][Mask(crc) LE32] behind, log / MANIFEST fragments [Mask(crc) LE32][len LE16][type] in front.
+enum Frame : uint32_t { kPlain = 0, kVlog = 1, kSst = 2, kLog = 3 };
+KVSEP_HD uint64_t lead(Frame f) { return f == kVlog ? 8 : f == kLog ? 7 : 0; }
 KVSEP_HD uint64_t trail(Frame f) { return f == kSst ? 5 : 0; }
 
 // Sums of lengths saturate at 2^64 - 1, the value fits() refuses: a run whose bytes leave 64 bits fits nowhere.
@@ -176,12 +176,17 @@ KVSEP_HD void align16(const uint32_t lo[4], const uint32_t hi[4], uint32_t sh, u
 KVSEP_HD uint32_t pass_segs(uint64_t ps, uint64_t e) { return e - ps < kWaveLanes ? uint32_t(e - ps) : kWaveLanes; }
 
 // The frame bytes, as the writers lay them down: byte i of the vlog header [Mask(crc) LE32][len LE32] (the length's low
-// 32 bits) and of the SST trailer [type][Mask(crc) LE32].
+// 32 bits), of the SST trailer [type][Mask(crc) LE32] and of the log fragment header.
 KVSEP_HD uint8_t vlog_header_byte(uint32_t masked, uint64_t len, uint32_t i) {
   return uint8_t((i < 4 ? masked : uint32_t(len)) >> (8 * (i & 3u)));
 }
 KVSEP_HD uint8_t sst_trailer_byte(uint8_t type, uint32_t masked, uint32_t i) {
   return i == 0 ? type : uint8_t(masked >> (8 * (i - 1)));
+}
+// Byte i of the log fragment header [Mask(crc) LE32][len LE16][type] (db/log_writer.cc:84-115; a fragment's length is
+// at most 32,761).
+KVSEP_HD uint8_t log_header_byte(uint32_t masked, uint64_t len, uint8_t type, uint32_t i) {
+  return i < 4 ? uint8_t(masked >> (8 * i)) : i < 6 ? uint8_t(len >> (8 * (i - 4))) : type;
 }
 
 }  // namespace pack

@@ -128,6 +128,10 @@ _SIGS = {
     "kvsep_log_records_device": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 7 +
                                  [ctypes.c_uint64] + [ctypes.c_void_p] * 9 + [ctypes.c_uint64] +
                                  [ctypes.c_void_p] * 4),
+    "kvsep_log_frame_layout": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_uint64] * 2 + [ctypes.c_void_p] * 4),
+    "kvsep_log_frame_device": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_uint64] * 2 + [ctypes.c_void_p] +
+                               [ctypes.c_uint64] + [ctypes.c_void_p] * 7 + [ctypes.c_uint64] +
+                               [ctypes.c_void_p] * 2 + [ctypes.c_uint64]),
     "kvsep_crc32c_group_extend_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                                                       ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]),
     "kvsep_crc32c_batch_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -507,6 +511,24 @@ class Context:
                                               _dptr(frag_off), _dptr(frag_len), _dptr(first), _dptr(whole),
                                               _dptr(nchain), _dptr(dst), dst_bytes, _dptr(rec_off), _dptr(rec_len),
                                               _dptr(end), _dptr(nwhole)), "kvsep_log_records_device")
+        return dst
+
+    def log_frame_device(self, base, off, length, dest_length, dst, dst_bytes, rec_at, frag_first, frag_off, frag_len,
+                         frag_at, frag_type, frag_crc, nfrag, written, keep=None, count=None, frag_cap=None,
+                         total_bytes=0, stream=None):
+        """kvsep_log_frame_device: the records [base + off[i], + length[i]) with keep[i] != 0 (keep optional), appended
+        to a log of dest_length bytes the way log::Writer::AddRecord does, into dst from offset 0, with no host step.
+        rec_at (int64, count) and frag_first (int64, count + 1) are log_frame_layout's; frag_off / frag_len / frag_at
+        (int64), frag_type (uint8) and frag_crc (int32) describe the physical records and are written for exactly
+        frag_cap elements; nfrag and written are one-element int64 device tensors.  rec_off / rec_len / whole of
+        log_records_device go in as off / length / keep."""
+        count = int(length.numel()) if count is None else count
+        frag_cap = int(frag_type.numel()) if frag_cap is None else frag_cap
+        _check(lib().kvsep_log_frame_device(self._h, _stream_handle(stream), _dptr(base), _dptr(off), _dptr(length),
+                                            _dptr(keep), count, dest_length, _dptr(dst), dst_bytes, _dptr(rec_at),
+                                            _dptr(frag_first), _dptr(frag_off), _dptr(frag_len), _dptr(frag_at),
+                                            _dptr(frag_type), _dptr(frag_crc), frag_cap, _dptr(nfrag), _dptr(written),
+                                            total_bytes), "kvsep_log_frame_device")
         return dst
 
     def concat_device(self, seg_crc, seg_len, first, out, init=None, count=None, nseg=None, stream=None):
@@ -936,6 +958,26 @@ def log_chains(type, accept, gap=None):
                                     None if g is None else g.ctypes.data_as(vp), count, first.ctypes.data_as(vp),
                                     whole.ctypes.data_as(vp), ctypes.byref(nwhole))
     return first, whole[:count], int(nchain), int(nwhole.value)
+
+
+def log_frame_layout(length, keep=None, dest_length=0):
+    """kvsep_log_frame_layout: where log::Writer::AddRecord puts records of these lengths appended to a log of
+    dest_length bytes -> (rec_at, frag_first, nfrag, written).  rec_at[i] = the offset of record i's first header from
+    the first appended byte (OFFSET_SKIP where keep[i] == 0); frag_first has count + 1 entries: record i is the physical
+    records [frag_first[i], frag_first[i + 1]); written = the appended bytes."""
+    length = np.ascontiguousarray(length, dtype=np.uint64)
+    count = length.size
+    if keep is not None and np.size(keep) != count:
+        raise ValueError("keep must have one element per record")
+    vp = ctypes.c_void_p
+    k = None if keep is None else np.ascontiguousarray(keep, dtype=np.uint8)
+    rec_at = np.zeros(max(count, 1), np.uint64)
+    frag_first = np.zeros(count + 1, np.uint64)
+    nfrag, written = ctypes.c_uint64(), ctypes.c_uint64()
+    _check(lib().kvsep_log_frame_layout(length.ctypes.data_as(vp), None if k is None else k.ctypes.data_as(vp), count,
+                                        dest_length, rec_at.ctypes.data_as(vp), frag_first.ctypes.data_as(vp),
+                                        ctypes.byref(nfrag), ctypes.byref(written)), "kvsep_log_frame_layout")
+    return rec_at[:count], frag_first, int(nfrag.value), int(written.value)
 
 
 def partition(length, parts: int) -> np.ndarray:
