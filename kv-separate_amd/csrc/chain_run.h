@@ -134,6 +134,8 @@ KVSEP_HD bool pads_frag(uint64_t k, uint64_t count, uint64_t cap) { return k >= 
 KVSEP_HD uint64_t pad_first(uint64_t count) { return count; }
 // The write kernel's grid: a lane per element of first[], the longest output (cap + 1).
 KVSEP_HD uint64_t write_tiles(uint64_t cap) { return tile_count(cap + 1); }
+// chain_reclen_kernel's grid: a lane per chain.
+KVSEP_HD uint64_t reclen_grid(uint64_t cap) { return (cap + kThreads - 1) / kThreads; }
 
 }  // namespace chain
 }  // namespace kvsep

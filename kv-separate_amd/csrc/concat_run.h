@@ -18,6 +18,11 @@
 #endif
 
 namespace kvsep {
+
+// crc32c_concat_kernel's workgroup (crc32c_concat.inc); here so that host-only code can include it.
+constexpr uint32_t kConcatThreads = 256;
+constexpr uint32_t kConcatWaves = kConcatThreads / 64;
+
 namespace concat {
 
 // A run of up to kShortMax segments is folded serially by one lane, a longer one by a whole wavefront.  One lane's fold
@@ -33,6 +38,9 @@ constexpr uint64_t kShortMax = 32;
 // one-segment blocks (5 -> 11 us for 65,536), the case the gather form meets most; 16 stays.
 constexpr uint32_t kWaveBlocks = 16;
 constexpr uint32_t kWaveLanes = 64;
+// Blocks per workgroup, and the grid of a batch of `count` blocks.
+constexpr uint64_t kPerWg = uint64_t(kConcatWaves) * kWaveBlocks;
+KVSEP_HD uint64_t grid_for(uint64_t count) { return (count + kPerWg - 1) / kPerWg; }
 // Segments one lane folds in one pass of a long run: a pass covers up to kPassSegs segments, so the lanes' chunks of
 // one pass sit within 12 KiB of seg_len / seg_crc.
 constexpr uint64_t kLaneSegs = 16;

@@ -16,8 +16,7 @@
 // long runs and over a run's passes is wave-uniform (a ballot, lane reads), so the tree's cross-lane steps -- DPP
 // row_shr within a 16-lane row, lane reads above it, as in the CRC kernels' lane tree -- run in full EXEC.
 
-constexpr uint32_t kConcatThreads = 256;
-constexpr uint32_t kConcatWaves = kConcatThreads / 64;
+// kConcatThreads, kConcatWaves and the grid (concat::grid_for): concat_run.h
 
 // X(n) = x^(8n) mod P over the set bits of n only: bit k of n < 2^61 is x^(2^(k + 3)) = x2n[k + 3]; the top three bits,
 // whose 8n leaves 64 bits, are raised as x^(2^k) and squared three times (exact for every n, unlike gf2_shift's n << 3).

@@ -243,7 +243,7 @@ int ensure_sst(Scratch& sc, uint64_t count, bool capturing = false) {
 
 // The list forms' tile arrays (crc32c_verdicts.inc): one total and one base per kListTile blocks.
 int ensure_list(Scratch& sc, uint64_t count, bool capturing = false) {
-  const uint64_t nt = (count + kListTile - 1) / kListTile;
+  const uint64_t nt = list_tile_count(count);
   if (nt <= sc.cap_tiles) return KVSEP_OK;
   if (capturing)
     return set_err(KVSEP_EINVAL, "a captured list call larger than kvsep_crc32c_reserve sized its capture set for");
@@ -342,19 +342,19 @@ struct ListOut {
 int launch_list(Scratch& sc, hipStream_t s, bool capturing, const uint32_t* out, const uint32_t* stored,
                 const uint64_t* nbad, const ListOut& l, uint64_t count) {
   if (!count || (!l.bad_cap && !l.ok)) return KVSEP_OK;
-  const uint64_t nt = (count + kListTile - 1) / kListTile;
+  const uint64_t nt = list_tile_count(count);
   const auto* nb = reinterpret_cast<const unsigned long long*>(nbad);
   if (l.bad_cap) {
     int rc = ensure_list(sc, count, capturing);
     if (rc) return rc;
   }
-  verdict_tile_count_kernel<<<unsigned(nt), 256, 0, s>>>(out, stored, count, nb, l.ok,
+  verdict_tile_count_kernel<<<unsigned(nt), kListThreads, 0, s>>>(out, stored, count, nb, l.ok,
                                                          l.bad_cap ? sc.d_tile_cnt : nullptr);
   KVSEP_HIP(hipGetLastError());
   if (!l.bad_cap) return KVSEP_OK;
-  verdict_tile_scan_kernel<<<1, 256, 0, s>>>(sc.d_tile_cnt, sc.d_tile_base, uint32_t(nt), nb);
+  verdict_tile_scan_kernel<<<1, kListThreads, 0, s>>>(sc.d_tile_cnt, sc.d_tile_base, uint32_t(nt), nb);
   KVSEP_HIP(hipGetLastError());
-  verdict_scatter_kernel<<<unsigned(nt), 256, 0, s>>>(out, stored, count, nb, sc.d_tile_base, l.bad_idx, l.bad_cap);
+  verdict_scatter_kernel<<<unsigned(nt), kListThreads, 0, s>>>(out, stored, count, nb, sc.d_tile_base, l.bad_idx, l.bad_cap);
   KVSEP_HIP(hipGetLastError());
   return KVSEP_OK;
 }
@@ -1142,9 +1142,8 @@ int launch_concat(kvsep_crc32c_ctx* c, hipStream_t s, const uint32_t* seg_crc, c
   if (!count) return KVSEP_OK;
   DeviceGuard dg(c->device);
   KVSEP_HIP(dg.err);
-  constexpr uint64_t kPerWg = uint64_t(kConcatWaves) * concat::kWaveBlocks;
-  crc32c_concat_kernel<<<unsigned((count + kPerWg - 1) / kPerWg), kConcatThreads, 0, s>>>(seg_crc, seg_len, first, init,
-                                                                                          out, count, nseg, c->d_tabs);
+  crc32c_concat_kernel<<<unsigned(concat::grid_for(count)), kConcatThreads, 0, s>>>(seg_crc, seg_len, first, init, out,
+                                                                                    count, nseg, c->d_tabs);
   KVSEP_HIP(hipGetLastError());
   return KVSEP_OK;
 }
@@ -1182,8 +1181,7 @@ int launch_pack(kvsep_crc32c_ctx* c, hipStream_t s, PackArgs a) {
   if (!a.count) return KVSEP_OK;
   DeviceGuard dg(c->device);
   KVSEP_HIP(dg.err);
-  constexpr uint64_t kPerWg = uint64_t(kPackWaves) * pack::kShortBlocks;
-  a.short_wgs = uint32_t((a.count + kPerWg - 1) / kPerWg);
+  a.short_wgs = pack::short_wgs(a.count);
   a.team = pack::team_size(a.count, 4u * uint32_t(c->num_cus > 0 ? c->num_cus : 256));
   const uint64_t grid = a.short_wgs + pack::chunk_count(a.count) * a.team;  // < 2^29 for count < 2^32
   crc32c_pack_kernel<F><<<unsigned(grid), kPackThreads, 0, s>>>(a);
@@ -1623,12 +1621,12 @@ int launch_log_accept_in(Scratch& sc, hipStream_t s, const LogAcceptCall& w) {
     log_block_kernel<<<unsigned(logrun::grid_for(nb)), logrun::kThreads, 0, s>>>(a);
     KVSEP_HIP(hipGetLastError());
   }
-  log_stop_kernel<<<1, logrun::kThreads, 0, s>>>(a.cand, nb, a.stop);
+  log_stop_kernel<<<logrun::kReduceGrid, logrun::kThreads, 0, s>>>(a.cand, nb, a.stop);
   KVSEP_HIP(hipGetLastError());
   log_accept_kernel<<<unsigned(logrun::pad_grid(nb, w.cap)), logrun::kThreads, 0, s>>>(a);
   KVSEP_HIP(hipGetLastError());
   if (w.dropped || w.bad_length) {
-    log_totals_kernel<<<1, logrun::kThreads, 0, s>>>(a.drop, a.badlen, nb, w.dropped, w.bad_length);
+    log_totals_kernel<<<logrun::kReduceGrid, logrun::kThreads, 0, s>>>(a.drop, a.badlen, nb, w.dropped, w.bad_length);
     KVSEP_HIP(hipGetLastError());
   }
   return KVSEP_OK;
@@ -1842,7 +1840,7 @@ int kvsep_log_records_device(kvsep_crc32c_ctx* c, void* stream, const void* base
       r = launch_offsets_in(sc, s, OffsetsCall{frag_len, first, whole, nullptr, 0, 0, 0, ~uint64_t(0), rec_off, end,
                                                nwhole, cap, cap});
     if (!r && rec_len && cap) {
-      chain_reclen_kernel<<<unsigned((cap + chain::kThreads - 1) / chain::kThreads), chain::kThreads, 0, s>>>(
+      chain_reclen_kernel<<<unsigned(chain::reclen_grid(cap)), chain::kThreads, 0, s>>>(
           sc.d_off_ext, rec_len, cap);
       if (hipGetLastError() != hipSuccess) r = set_err(KVSEP_EHIP, "chain_reclen_kernel launch");
     }

@@ -27,8 +27,7 @@
 // The host cannot know which part a block belongs to (the lengths are on the device), so both parts always run; the
 // second costs a descriptor read where no block is long.
 
-constexpr uint32_t kPackThreads = 256;
-constexpr uint32_t kPackWaves = kPackThreads / 64;
+// kPackThreads, kPackWaves and the grid (pack::short_wgs, pack::chunk_count, pack::team_size): pack_run.h
 
 struct PackPlain {
   static constexpr pack::Frame kFrame = pack::kPlain;

@@ -18,8 +18,7 @@
 // returns after that one load (the count kernel only when no ok[] is wanted), so nothing reads the tile arrays: a
 // replay never reads a word it did not write.
 
-constexpr uint32_t kListTile = 1024;  // blocks per tile: 4 waves x 4 rows of 64
-constexpr int kListRows = 4;
+// kListTile (1024 blocks: 4 waves x 4 rows of 64), kListRows and kListThreads: offsets_run.h
 
 __device__ __forceinline__ unsigned long long ld_word64(const unsigned long long* p) {
   return *reinterpret_cast<const __attribute__((address_space(1))) unsigned long long*>(reinterpret_cast<uintptr_t>(p));

@@ -38,6 +38,7 @@ KVSEP_HD uint64_t block_begin(uint64_t blk) { return blk * kBlock; }
 KVSEP_HD uint64_t block_end(uint64_t blk, uint64_t n) { return n - blk * kBlock > kBlock ? (blk + 1) * kBlock : n; }
 KVSEP_HD bool block_full(uint64_t begin, uint64_t end) { return end - begin == kBlock; }
 KVSEP_HD uint64_t grid_for(uint64_t items) { return (items + kThreads - 1) / kThreads; }
+constexpr uint32_t kReduceGrid = 1;  // log_stop_kernel and log_totals_kernel: one workgroup strides over the blocks
 // The grid of the two kernels whose lanes walk a block each and then share out the padding from min(*nrec, cap) to
 // cap, lane g taking elements g, g + lanes, ...: a lane per block, about kPadPerLane elements a lane, one workgroup at
 // least (an empty image still has its padding and its words to write).

@@ -18,6 +18,14 @@
 #include "concat_run.h"
 
 namespace kvsep {
+
+// The list pass of the verify forms (crc32c_verdicts.inc) has no rules header of its own; its launch geometry lives here,
+// next to the tile it shares with the offsets pass, so that host-only code can include it.
+constexpr uint32_t kListTile = 1024;  // blocks per tile: 4 waves x 4 rows of 64
+constexpr int kListRows = 4;
+constexpr uint32_t kListThreads = 256;
+KVSEP_HD uint64_t list_tile_count(uint64_t count) { return (count + kListTile - 1) / kListTile; }
+
 namespace offsets {
 
 using concat::Run;

@@ -17,6 +17,11 @@
 #include "concat_run.h"
 
 namespace kvsep {
+
+// crc32c_pack_kernel's workgroup (crc32c_pack.inc); here so that host-only code can include it.
+constexpr uint32_t kPackThreads = 256;
+constexpr uint32_t kPackWaves = kPackThreads / 64;
+
 namespace pack {
 
 using concat::Run;
@@ -81,6 +86,12 @@ KVSEP_HD uint64_t chunk_count(uint64_t count) { return (count + kChunkBlocks - 1
 KVSEP_HD uint32_t team_size(uint64_t count, uint32_t wgs) {
   const uint64_t t = wgs / chunk_count(count ? count : 1);
   return uint32_t(t < kMinTeam ? kMinTeam : t);
+}
+// The first part of the grid: short_wgs workgroups whose waves take kShortBlocks blocks each (then `team` workgroups per
+// chunk: short_wgs + chunk_count * team in all).
+KVSEP_HD uint32_t short_wgs(uint64_t count) {
+  constexpr uint64_t per_wg = uint64_t(kPackWaves) * kShortBlocks;
+  return uint32_t((count + per_wg - 1) / per_wg);
 }
 // Tile t of the block in lane `slot` of its chunk goes to wave (slot + t) mod team_waves of the chunk's team: the tiles
 // of one block go round the team, and the first tiles of neighbouring blocks start on different waves.

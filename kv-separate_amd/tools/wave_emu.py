@@ -38,6 +38,9 @@ class Memory:
     def __init__(self, track: bool = False):
         self.regions = []  # (base, np.uint8 array)
         self.marks = {} if track else None  # region base -> (read marks, write marks), one np.bool_ per byte
+        self.scratch = None  # declare_scratch: region base -> one "written by an emulated store" mark per byte
+        self.uninit = []     # (address, bytes, instruction line) of every read of a scratch byte no store has written
+        self.line = 0        # the assembly line of the instruction being executed (Workgroup.step sets it)
         self.next = 0x10000000
         self.payload = None  # batch_memory: (guard region base, its size, payload address, payload size)
 
@@ -61,16 +64,34 @@ class Memory:
                 return arr, addr - base
         raise EmuError("bad address 0x%x (+%d)" % (addr, n))
 
+    def declare_scratch(self, base: int):
+        """Opt-in initialised-ness mark for the region at `base` (the call's scratch): from now on a read() of one of its
+        bytes that no write() has stored since is recorded in self.uninit as (address, bytes, instruction line).  What
+        alloc() or view() put there does not count: a replay must not depend on it."""
+        arr, o = self.find(base, 1)
+        assert o == 0, "declare_scratch takes a region's base"
+        if self.scratch is None:
+            self.scratch = {}
+        self.scratch[base] = np.zeros(arr.size, dtype=bool)
+
     def read(self, addr: int, n: int) -> bytes:
         arr, o = self.find(addr, n)
         if self.marks is not None:
             self.marks[addr - o][0][o:o + n] = True
+        if self.scratch is not None:
+            init = self.scratch.get(addr - o)
+            if init is not None and not init[o:o + n].all():
+                self.uninit.append((addr, n, self.line))
         return arr[o:o + n].tobytes()
 
     def write(self, addr: int, data: bytes):
         arr, o = self.find(addr, len(data))
         if self.marks is not None:
             self.marks[addr - o][1][o:o + len(data)] = True
+        if self.scratch is not None:
+            init = self.scratch.get(addr - o)
+            if init is not None:
+                init[o:o + len(data)] = True
         arr[o:o + len(data)] = np.frombuffer(data, dtype=np.uint8)
 
     def r32(self, addr):
@@ -379,6 +400,7 @@ class Workgroup:
         k = self.insns[w.pc]
         w.pc += 1
         w.count += 1
+        self.mem.line = k.line
         op, o = k.op, k.ops
         try:
             self.exec_insn(w, k, op, o)
@@ -615,6 +637,23 @@ class Workgroup:
             v = g(o[1])
             w.sset(o[0], (v & -v).bit_length() - 1 if v else M32)
             return
+        if op in ('s_flbit_i32_b32', 's_flbit_i32_b64'):  # zeros in front of the highest set bit; -1 for 0
+            wd = 64 if op.endswith('64') else 32
+            v = g(o[1], wd)
+            w.sset(o[0], wd - v.bit_length() if v else M32)
+            return
+        if op == 's_brev_b32':
+            w.sset(o[0], int('{:032b}'.format(g(o[1]))[::-1], 2))
+            return
+        m = re.match(r's_cmpk_(eq|lg|lt|le|gt|ge)_(u32|i32)$', op)
+        if m:  # the 16-bit immediate zero-extended (u32) or sign-extended (i32)
+            c, t = m.group(1), m.group(2)
+            a, b = g(o[0]), g(o[1]) & 0xFFFF
+            if t == 'i32':
+                a = a - (1 << 32) if a >> 31 else a
+                b = b - 0x10000 if b & 0x8000 else b
+            w.scc = int({'eq': a == b, 'lg': a != b, 'lt': a < b, 'le': a <= b, 'gt': a > b, 'ge': a >= b}[c])
+            return
         raise EmuError('unknown SALU ' + k.text)
 
     # ------------------------------------------------------------------------------------------------------------
@@ -630,6 +669,23 @@ class Workgroup:
                 a = w.vget(vaddr_t).astype(np.uint64) + np.uint64(base)
             return a + np.uint64(off_imm & M64 if off_imm >= 0 else (off_imm + (1 << 64)))
 
+        if op in ('global_load_ubyte', 'global_load_sbyte', 'global_load_ushort', 'global_load_sshort'):
+            nb = 1 if 'byte' in op else 2
+            a = addrs(o[1], o[2] if len(o) > 2 else 'off')
+            r = int(REG.match(o[0]).group(2))
+            for l in np.nonzero(act)[0]:
+                x = int.from_bytes(mem.read(int(a[l]), nb), 'little')
+                if op in ('global_load_sbyte', 'global_load_sshort') and x >> (8 * nb - 1):
+                    x |= M32 & ~((1 << (8 * nb)) - 1)
+                w.v[r][l] = x
+            return
+        if op in ('global_store_byte', 'global_store_short'):
+            nb = 1 if op.endswith('byte') else 2
+            a = addrs(o[0], o[2] if len(o) > 2 else 'off')
+            d = w.vget(o[1])
+            for l in np.nonzero(act)[0]:
+                mem.write(int(a[l]), (int(d[l]) & ((1 << (8 * nb)) - 1)).to_bytes(nb, 'little'))
+            return
         if op.startswith('global_load_'):
             n = {'global_load_dword': 1, 'global_load_dwordx2': 2, 'global_load_dwordx3': 3,
                  'global_load_dwordx4': 4}[op]
@@ -702,6 +758,35 @@ class Workgroup:
                 ad = int(a[l])
                 self.lds[ad:ad + 4 * n] = np.frombuffer(
                     struct.pack('<%dI' % n, *[int(w.v[first + i][l]) for i in range(n)]), dtype=np.uint8)
+            return
+        m = re.match(r'ds_(read|write)2(st64)?_b(32|64)$', op)
+        if m:  # two elements at addr + offset0 * size and addr + offset1 * size (st64: * 64 * size)
+            n = int(m.group(3)) // 32
+            unit = 4 * n * (64 if m.group(2) else 1)
+            offs = [int(k.mods.get('offset0', '0'), 0) * unit, int(k.mods.get('offset1', '0'), 0) * unit]
+            if m.group(1) == 'read':
+                a = w.vget(o[1]).astype(np.int64)
+                rm = REG.match(o[0])
+                first = int(rm.group(2)) if rm.group(1) else int(rm.group(4))
+                for l in np.nonzero(act)[0]:
+                    for e in range(2):
+                        ad = int(a[l]) + offs[e]
+                        if ad < 0 or ad + 4 * n > self.lds.size:
+                            raise EmuError('line %d: LDS address 0x%x out of range' % (k.line, ad))
+                        vals = struct.unpack('<%dI' % n, self.lds[ad:ad + 4 * n].tobytes())
+                        for i in range(n):
+                            w.v[first + e * n + i][l] = vals[i]
+            else:
+                a = w.vget(o[0]).astype(np.int64)
+                for l in np.nonzero(act)[0]:
+                    for e in range(2):
+                        ad = int(a[l]) + offs[e]
+                        if ad < 0 or ad + 4 * n > self.lds.size:
+                            raise EmuError('line %d: LDS address 0x%x out of range' % (k.line, ad))
+                        rm = REG.match(o[1 + e])
+                        first = int(rm.group(2)) if rm.group(1) else int(rm.group(4))
+                        self.lds[ad:ad + 4 * n] = np.frombuffer(
+                            struct.pack('<%dI' % n, *[int(w.v[first + i][l]) for i in range(n)]), dtype=np.uint8)
             return
         if op in ('ds_add_rtn_u32', 'ds_add_u32'):  # LDS atomic add; active lanes in lane order
             ret = op == 'ds_add_rtn_u32'
@@ -790,6 +875,15 @@ class Workgroup:
         V = w.vget
         base = re.sub(r'_(e32|e64|sdwa|dpp)$', '', op)
         # compares
+        m = re.match(r'v_cmp_(eq|ne|lt|le|gt|ge|lg)_(u16|i16)$', base)
+        if m:  # the low 16 bits of each operand (an inline constant is taken as 16 bits too)
+            c, t = m.group(1), m.group(2)
+            dst, a_t, b_t = ('vcc', o[-2], o[-1]) if op.endswith('_e32') else (o[0], o[1], o[2])
+            a, b = V(a_t).astype(np.uint16), V(b_t).astype(np.uint16)
+            if t == 'i16':
+                a, b = a.view(np.int16), b.view(np.int16)
+            w.sset(dst, Wave.pack(CMP[c](a, b) & act))
+            return
         m = re.match(r'v_cmp_(eq|ne|lt|le|gt|ge|lg)_(u32|i32|u64|i64)$', base)
         if m:
             c, t = m.group(1), m.group(2)
@@ -871,6 +965,39 @@ class Workgroup:
                     r |= ta & tb & tc
             w.vset(o[0], r)
             return
+        if base == 'v_bitop3_b16':  # VOP3 with op_sel 0: the low halves, the destination's high half kept
+            a, b, c = V(o[1]), V(o[2]), V(o[3])
+            imm = int(k.mods['bitop3'], 0)
+            r = np.zeros(64, dtype=np.uint32)
+            for idx in range(8):
+                if (imm >> idx) & 1:
+                    r |= (a if idx & 4 else ~a) & (b if idx & 2 else ~b) & (c if idx & 1 else ~c)
+            w.vset(o[0], (V(o[0]) & u(0xFFFF0000)) | (r & u(0xFFFF)))
+            return
+        if base == 'v_or3_b32':
+            w.vset(o[0], V(o[1]) | V(o[2]) | V(o[3]))
+            return
+        if base == 'v_add_u16':  # VOP2 16-bit: the sum modulo 2^16, the high half of the destination zero
+            w.vset(o[0], (V(o[1]) + V(o[2])) & u(0xFFFF))
+            return
+        if base == 'v_alignbyte_b32':
+            a, b, sh = V(o[1]).astype(np.uint64), V(o[2]).astype(np.uint64), ((V(o[3]) & u(3)) * u(8)).astype(np.uint64)
+            w.vset(o[0], (((a << np.uint64(32)) | b) >> sh) & np.uint64(M32))
+            return
+        if base in ('v_mul_u32_u24', 'v_mul_hi_u32_u24'):
+            p = (V(o[1]) & u(0xFFFFFF)).astype(np.uint64) * (V(o[2]) & u(0xFFFFFF)).astype(np.uint64)
+            w.vset(o[0], ((p if base == 'v_mul_u32_u24' else p >> np.uint64(32)) & np.uint64(M32)).astype(np.uint32))
+            return
+        if base in ('v_ffbh_u32', 'v_ffbl_b32'):  # zeros in front of the highest / behind the lowest set bit; -1 for 0
+            x = V(o[1])
+            r = np.array([M32 if not int(t) else (32 - int(t).bit_length() if base == 'v_ffbh_u32' else
+                                                  (int(t) & -int(t)).bit_length() - 1) for t in x], dtype=np.uint32)
+            w.vset(o[0], r)
+            return
+        if base == 'v_bcnt_u32_b32':
+            x = V(o[1])
+            w.vset(o[0], np.array([bin(int(t)).count('1') for t in x], dtype=np.uint32) + V(o[2]))
+            return
         if base == 'v_and_or_b32':
             w.vset(o[0], (V(o[1]) & V(o[2])) | V(o[3]))
             return
@@ -888,7 +1015,8 @@ class Workgroup:
             r = V(o[1]).astype(np.uint64) + V(o[2]).astype(np.uint64) + V(o[3]).astype(np.uint64)
             w.vset(o[0], (r & np.uint64(M32)).astype(np.uint32))
             return
-        if base in ('v_add_co_u32', 'v_sub_co_u32', 'v_subrev_co_u32', 'v_addc_co_u32', 'v_subb_co_u32'):
+        if base in ('v_add_co_u32', 'v_sub_co_u32', 'v_subrev_co_u32', 'v_addc_co_u32', 'v_subb_co_u32',
+                    'v_subbrev_co_u32'):
             dst, cd, a_t, b_t = o[0], o[1], o[2], o[3]
             a, b = V(a_t).astype(np.int64), V(b_t).astype(np.int64)
             cin = Wave.bits(w.sget(o[4], 64)).astype(np.int64) if len(o) > 4 else 0
@@ -903,6 +1031,9 @@ class Workgroup:
                 co = r < 0
             elif base == 'v_subrev_co_u32':
                 r = b - a
+                co = r < 0
+            elif base == 'v_subbrev_co_u32':
+                r = b - a - cin
                 co = r < 0
             else:
                 r = a - b - cin
@@ -1097,6 +1228,108 @@ def launch_plain(mem: Memory, asm: str, name: str, threads: int, args: bytes, gr
     struct.pack_into("<III", ka, len(args), grid, 1, 1)
     struct.pack_into("<HHH", ka, len(args) + 12, threads, 1, 1)
     struct.pack_into("<H", ka, len(args) + 64, 1)
+    insns, labels = kernel_code(asm, name)
+    d_ka = mem.alloc(len(ka), data=bytes(ka))
+    return sum(Workgroup(mem, insns, labels, threads, group_segment_bytes(asm, name), d_ka, g).run()
+               for g in range(grid))
+
+
+def kernel_args(asm: str, name: str):
+    """The kernel's arguments from its .args metadata in the assembly: [(offset, size, value_kind)], the hidden ones
+    (hidden_block_count_x, ...) included."""
+    key = ("args", asm, name, os.path.getmtime(asm))
+    if key not in _FN_CACHE:
+        text = open(asm).read()
+        md = text[text.index("amdhsa.kernels:"):]
+        for ent in md.split("\n  - .agpr_count")[1:]:
+            m = re.search(r"\.name:\s+(\S+)", ent)
+            if m and m.group(1) == name:
+                body = ent[ent.index(".args:"):ent.index(".group_segment_fixed_size")] if ".args:" in ent else ""
+                args = []
+                for a in body.split("\n      - ")[1:]:
+                    f = dict(re.findall(r"\.(\w+):\s+(\S+)", a))
+                    args.append((int(f["offset"]), int(f["size"]), f["value_kind"]))
+                _FN_CACHE[key] = args
+                break
+        else:
+            raise EmuError("no metadata for kernel " + name)
+    return _FN_CACHE[key]
+
+
+C_SIZES = {"uint64_t": 8, "uint32_t": 4, "uint16_t": 2, "uint8_t": 1, "unsigned long long": 8, "int": 4, "unsigned": 4}
+
+
+def struct_fields(src: str, struct: str) -> dict:
+    """{field: (offset, size)} of a plain struct of pointers and fixed-width integers, read from its definition in the
+    source file `src` and laid out by the C rules (every member aligned to its size, the struct to its widest)."""
+    text = open(src).read()
+    m = re.search(r"struct\s+" + re.escape(struct) + r"\s*\{(.*?)\n\};", text, re.S)
+    if not m:
+        raise EmuError("struct %s not found in %s" % (struct, src))
+    fields, at, widest = {}, 0, 1
+    for stmt in re.sub(r"//[^\n]*", "", m.group(1)).split(";"):
+        stmt = " ".join(stmt.split())
+        if not stmt:
+            continue
+        names = [n.strip() for n in stmt.split(",")]
+        head = names[0].rsplit(" ", 1) if "*" not in names[0] else [names[0][:names[0].rindex("*") + 1],
+                                                                    names[0][names[0].rindex("*") + 1:]]
+        ctype, names[0] = head[0].strip(), head[1].strip()
+        if ctype.endswith("*"):
+            size = 8
+        else:
+            ctype = ctype.replace("const ", "").strip()
+            if ctype not in C_SIZES:
+                raise EmuError("struct %s: type %r" % (struct, ctype))
+            size = C_SIZES[ctype]
+        for n in names:
+            at = (at + size - 1) // size * size
+            fields[n.lstrip("* ")] = (at, size)
+            at += size
+            widest = max(widest, size)
+    fields["sizeof"] = ((at + widest - 1) // widest * widest, 0)
+    return fields
+
+
+def struct_kernarg(asm: str, name: str, src: str, struct: str, values: dict) -> bytes:
+    """The kernarg image of a kernel that takes one struct by value: the fields' offsets from struct_fields, checked
+    against the size the kernel's .args metadata gives its by-value argument (the metadata holds the struct as one
+    argument, not its members).  Fields not in `values` are zero (a null pointer)."""
+    fields = struct_fields(src, struct)
+    explicit = [a for a in kernel_args(asm, name) if not a[2].startswith("hidden_")]
+    if len(explicit) != 1 or explicit[0][2] != "by_value" or explicit[0][1] != fields["sizeof"][0]:
+        raise EmuError("%s: struct %s laid out as %d bytes, the kernel's arguments are %s" % (
+            name, struct, fields["sizeof"][0], explicit))
+    img = bytearray(explicit[0][1])
+    for k, v in values.items():
+        o, size = fields[k]
+        img[o:o + size] = int(v).to_bytes(size, "little")
+    return bytes(img)
+
+
+def args_kernarg(asm: str, name: str, values) -> bytes:
+    """The kernarg image of a kernel with ordinary arguments: values in order, placed by the .args metadata."""
+    explicit = [a for a in kernel_args(asm, name) if not a[2].startswith("hidden_")]
+    if len(explicit) != len(values):
+        raise EmuError("%s takes %d arguments, %d given" % (name, len(explicit), len(values)))
+    img = bytearray(max(o + s for o, s, _ in explicit))
+    for (o, size, _), v in zip(explicit, values):
+        img[o:o + size] = int(v).to_bytes(size, "little")
+    return bytes(img)
+
+
+def launch_args(mem: Memory, asm: str, name: str, threads: int, args: bytes, grid: int) -> int:
+    """Run every workgroup of a kernel whose explicit kernarg image is `args` (struct_kernarg / args_kernarg); the
+    hidden arguments the kernel declares go where its metadata puts them.  Returns the wave-instructions executed."""
+    hidden = {k: (o, s) for o, s, k in kernel_args(asm, name) if k.startswith("hidden_")}
+    ka = bytearray(max([len(args)] + [o + s for o, s in hidden.values()]) + 256)
+    ka[:len(args)] = args
+    for k, v in (("hidden_block_count_x", grid), ("hidden_block_count_y", 1), ("hidden_block_count_z", 1),
+                 ("hidden_group_size_x", threads), ("hidden_group_size_y", 1), ("hidden_group_size_z", 1),
+                 ("hidden_grid_dims", 1)):
+        if k in hidden:
+            o, size = hidden[k]
+            ka[o:o + size] = int(v).to_bytes(size, "little")
     insns, labels = kernel_code(asm, name)
     d_ka = mem.alloc(len(ka), data=bytes(ka))
     return sum(Workgroup(mem, insns, labels, threads, group_segment_bytes(asm, name), d_ka, g).run()

@@ -209,3 +209,258 @@ def test_emulated_wide_planned_with_combine(env, verify):
         _, _, fb, nb, _ = E.run_planned_batch(ASM, PIECES % (1, 1, 1), COMBINE % 1, data, off, ln, tabs,
                                               expect=_planted(exp, mask, np.array([], np.int64)))
         assert (fb, nb) == (-1, 0)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The opcodes the layout, log and list kernels add (tests/test_isa_envelope_framing.py): one instruction at a time
+# against a plain Python integer definition, on edge operands, with every third lane masked off by EXEC -- an inactive
+# lane keeps its destination, and writes 0 into a carry / compare mask.
+M32 = 0xFFFFFFFF
+EDGE32 = [0, 1, 2, 3, 0x7F, 0x80, 0xFF, 0x100, 0x7FFF, 0x8000, 0xFFFF, 0x10000, 0xFFFFFF, 0x1000000, 0x7FFFFFFF,
+          0x80000000, 0x80000001, 0xFFFFFFFE, 0xFFFFFFFF, 0x12345678, 0x89ABCDEF, 0x00FF00FF, 31, 32, 63, 64]
+EXEC = sum(1 << l for l in range(64) if l % 3 != 2)
+KEPT = 0x5A5A5A5A  # what an inactive lane's destination holds before and after
+
+
+class One:
+    """A wave for single instructions: v1, v2, v3 hold edge operands in every pairing, v0 is the destination."""
+
+    def __init__(self):
+        import wave_emu as E
+        self.E = E
+        self.wg = E.Workgroup(E.Memory(), [], {}, 64, 65536, 0, 0)
+        self.w = self.wg.waves[0]
+        self.w.exec = EXEC
+
+    def run(self, text):
+        k = self.E.Insn(0, text)
+        self.wg.exec_insn(self.w, k, k.op, k.ops)
+
+    def lanes(self, *cols):
+        for r, c in enumerate(cols, 1):
+            self.w.v[r] = np.array(c, np.uint32)
+        self.w.v[0] = np.full(64, KEPT, np.uint32)
+
+    def check(self, text, want, a, b=None, c=None):
+        """want(a, b, c) per active lane against v0 after `text`; the operand triples cover EDGE32 in rotation."""
+        for rot_b in range(0, len(EDGE32), 5):
+            for rot_c in ((0, 7) if c is not None else (0,)):
+                A = [EDGE32[l % len(EDGE32)] for l in range(64)]
+                B = [EDGE32[(l + rot_b) % len(EDGE32)] for l in range(64)]
+                C = [EDGE32[(l * 3 + rot_c) % len(EDGE32)] for l in range(64)]
+                self.lanes(A, B, C)
+                self.run(text)
+                for l in range(64):
+                    exp = want(A[l], B[l], C[l]) & M32 if EXEC >> l & 1 else KEPT
+                    assert int(self.w.v[0][l]) == exp, "%s lane %d: a=%#x b=%#x c=%#x -> %#x, want %#x" % (
+                        text, l, A[l], B[l], C[l], int(self.w.v[0][l]), exp)
+
+
+def _bitop3(imm, a, b, c):
+    r = 0
+    for i in range(8):
+        if imm >> i & 1:
+            r |= (a if i & 4 else ~a) & (b if i & 2 else ~b) & (c if i & 1 else ~c)
+    return r & M32
+
+
+VALU_CASES = [
+    ("v_alignbyte_b32 v0, v1, v2, v3", lambda a, b, c: ((a << 32 | b) >> 8 * (c & 3))),
+    ("v_add_u16_e32 v0, v1, v2", lambda a, b, c: (a + b) & 0xFFFF),
+    ("v_or3_b32 v0, v1, v2, v3", lambda a, b, c: a | b | c),
+    ("v_bitop3_b16 v0, v1, v2, v3 bitop3:0xc3", lambda a, b, c: (KEPT & 0xFFFF0000) | (_bitop3(0xC3, a, b, c) & 0xFFFF)),
+    ("v_bitop3_b16 v0, v1, 1, v3 bitop3:0xc", lambda a, b, c: (KEPT & 0xFFFF0000) | (_bitop3(0xC, a, 1, c) & 0xFFFF)),
+    ("v_mul_u32_u24_e32 v0, v1, v2", lambda a, b, c: (a & 0xFFFFFF) * (b & 0xFFFFFF)),
+    ("v_mul_hi_u32_u24_e32 v0, v1, v2", lambda a, b, c: ((a & 0xFFFFFF) * (b & 0xFFFFFF)) >> 32),
+    ("v_ffbh_u32_e32 v0, v1", lambda a, b, c: 32 - a.bit_length() if a else M32),
+    ("v_ffbl_b32_e32 v0, v1", lambda a, b, c: (a & -a).bit_length() - 1 if a else M32),
+    ("v_bcnt_u32_b32 v0, v1, v2", lambda a, b, c: bin(a).count("1") + b),
+]
+
+
+@pytest.mark.parametrize("text,want", VALU_CASES, ids=[t.split()[0] for t, _ in VALU_CASES])
+def test_added_valu_opcode(text, want):
+    One().check(text, want, True, True, True)
+
+
+@pytest.mark.parametrize("text", ["v_subbrev_co_u32_e32 v0, vcc, v1, v2, vcc",
+                                  "v_subbrev_co_u32_e64 v0, s[10:11], v1, v2, s[12:13]"])
+def test_added_subbrev(text):
+    """d = src1 - src0 - borrow in; borrow out per active lane, 0 for an inactive one.  Borrow in 0, all ones, mixed."""
+    for cin in (0, (1 << 64) - 1, 0xF0F0F0F0AAAA5555):
+        o = One()
+        A = [EDGE32[l % len(EDGE32)] for l in range(64)]
+        B = [EDGE32[(l * 7 + 3) % len(EDGE32)] for l in range(64)]
+        B[:6] = A[:6]  # equal operands: the borrow in alone decides
+        o.lanes(A, B)
+        o.w.vcc = cin
+        o.w.s[12], o.w.s[13] = cin & M32, cin >> 32
+        o.run(text)
+        out = o.w.vcc if "e32" in text else o.w.s[10] | o.w.s[11] << 32
+        for l in range(64):
+            act, ci = EXEC >> l & 1, cin >> l & 1
+            r = B[l] - A[l] - ci
+            assert int(o.w.v[0][l]) == (r & M32 if act else KEPT), (text, l, hex(cin))
+            assert out >> l & 1 == (1 if act and r < 0 else 0), (text, l, hex(cin))
+
+
+CMP_PY = {"eq": lambda a, b: a == b, "ne": lambda a, b: a != b, "lt": lambda a, b: a < b, "le": lambda a, b: a <= b,
+          "gt": lambda a, b: a > b, "ge": lambda a, b: a >= b}
+
+
+@pytest.mark.parametrize("t", ["u16", "i16"])
+@pytest.mark.parametrize("c", list(CMP_PY))
+def test_added_compare16(c, t):
+    """16-bit compares see the low halves only (as signed for i16); e32 writes VCC, e64 an SGPR pair."""
+    def half(x):
+        x &= 0xFFFF
+        return x - 0x10000 if t == "i16" and x & 0x8000 else x
+    for text, dst in (("v_cmp_%s_%s_e32 vcc, v1, v2" % (c, t), "vcc"), ("v_cmp_%s_%s_e64 s[20:21], v1, v2" % (c, t), "s")):
+        o = One()
+        A = [EDGE32[l % len(EDGE32)] for l in range(64)]
+        B = [EDGE32[(l * 5 + 1) % len(EDGE32)] for l in range(64)]
+        B[:8] = [x ^ 0xABCD0000 for x in A[:8]]  # equal low halves, different high halves
+        o.lanes(A, B)
+        o.run(text)
+        out = o.w.vcc if dst == "vcc" else o.w.s[20] | o.w.s[21] << 32
+        for l in range(64):
+            assert out >> l & 1 == int(bool(EXEC >> l & 1) and CMP_PY[c](half(A[l]), half(B[l]))), (text, l)
+    o = One()  # an inline constant operand
+    o.lanes([0, 1, 0x10000, 0x1FFFF] * 16, [0] * 64)
+    o.run("v_cmp_ne_u16_e32 vcc, 0, v1")
+    assert o.w.vcc == sum(1 << l for l in range(64) if EXEC >> l & 1 and l % 4 in (1, 3))
+
+
+def test_added_salu_opcodes():
+    o = One()
+    for v in [0, 1, 2, 0x80000000, M32, 0x00010000, 0x7FFFFFFF, 1 << 63, (1 << 64) - 1, 1 << 32, 0x0000FFFF00000000]:
+        o.w.s[4], o.w.s[5] = v & M32, v >> 32
+        o.run("s_flbit_i32_b64 s6, s[4:5]")
+        assert o.w.s[6] == (64 - v.bit_length() if v else M32), hex(v)
+        o.run("s_flbit_i32_b32 s6, s4")
+        assert o.w.s[6] == (32 - (v & M32).bit_length() if v & M32 else M32), hex(v)
+        o.run("s_brev_b32 s6, s4")
+        assert o.w.s[6] == int("{:032b}".format(v & M32)[::-1], 2), hex(v)
+        a, b = v & M32, 0x1234FFFF00FF00FF & M32
+        o.w.s[7] = b
+        o.w.s[8], o.w.s[9] = 0xFFFFFFFF, 0x0F0F0F0F
+        o.run("s_nor_b64 s[10:11], s[4:5], s[8:9]")
+        want = ~(v | 0x0F0F0F0FFFFFFFFF) & ((1 << 64) - 1)
+        assert (o.w.s[10] | o.w.s[11] << 32, o.w.scc) == (want, int(want != 0)), hex(v)
+    for a in (0, 1, 0x7FFF, 0x8000, 0xFFFF, 0x10000, M32):
+        for imm in (0, 1, 0x7FFF, 0x8000, 0xFFFF):
+            o.w.s[4] = a
+            o.run("s_cmpk_lt_u32 s4, 0x%x" % imm)
+            assert o.w.scc == int(a < imm), (a, imm)  # the immediate zero-extends: 0x8000 is 32768
+            o.run("s_cmpk_ge_u32 s4, 0x%x" % imm)
+            assert o.w.scc == int(a >= imm), (a, imm)
+            o.run("s_cmpk_lt_i32 s4, 0x%x" % imm)
+            sa, si = a - (1 << 32) if a >> 31 else a, imm - 0x10000 if imm & 0x8000 else imm
+            assert o.w.scc == int(sa < si), (a, imm)
+
+
+def test_added_lds_pair_opcodes():
+    """ds_read2 / ds_write2 (_b32, _b64; st64: offsets in units of 64 elements): two elements at addr + offset0 * size and
+    addr + offset1 * size, against the single-element ops' view of the same LDS; inactive lanes neither store nor load."""
+    for op, n, unit in (("2_b32", 1, 4), ("2_b64", 2, 8), ("2st64_b64", 2, 512), ("2st64_b32", 1, 256)):
+        for o0, o1 in ((0, 1), (3, 255 if unit < 256 else 4), (61, 62) if unit < 256 else (1, 0)):
+            o = One()
+            # st64: a lane per element inside the first 64-element unit, so no two lanes' pairs overlap; else every lane
+            # at address 0 (the last active lane's data stays)
+            addr = np.arange(64, dtype=np.uint32) * np.uint32(4 * n if unit >= 256 else 0)
+            o.w.v[1] = addr
+            data = [np.arange(64, dtype=np.uint32) * np.uint32(0x01010101 * (r + 1)) + np.uint32(r << 28)
+                    for r in range(4)]
+            for r in range(4):
+                o.w.v[4 + r] = data[r]
+            regs = ("v4", "v5") if n == 1 else ("v[4:5]", "v[6:7]")
+            o.run("ds_write%s v1, %s, %s offset0:%d offset1:%d" % (op, regs[0], regs[1], o0, o1))
+            last = max(l for l in range(64) if EXEC >> l & 1)
+            lds = o.wg.lds
+            for e, off in enumerate((o0, o1)):
+                for l in (range(64) if unit >= 256 else [last]):
+                    at = int(addr[l]) + off * unit
+                    got = [int.from_bytes(lds[at + 4 * i:at + 4 * i + 4].tobytes(), "little") for i in range(n)]
+                    if unit >= 256 and not EXEC >> l & 1:
+                        assert got == [0] * n, (op, l)  # an inactive lane stored nothing
+                    else:
+                        assert got == [int(data[e * n + i][l]) for i in range(n)], (op, o0, o1, l, e)
+            for r in range(8, 12):
+                o.w.v[r] = np.full(64, KEPT, np.uint32)
+            dst = "v[8:9]" if n == 1 else "v[8:11]"
+            o.run("ds_read%s %s, v1 offset0:%d offset1:%d" % (op, dst, o0, o1))
+            for l in range(64):
+                for e, off in enumerate((o0, o1)):
+                    at = int(addr[l]) + off * unit
+                    for i in range(n):
+                        want = int.from_bytes(lds[at + 4 * i:at + 4 * i + 4].tobytes(), "little") if EXEC >> l & 1 \
+                            else KEPT
+                        assert int(o.w.v[8 + e * n + i][l]) == want, (op, o0, o1, l, e, i)
+
+
+def test_added_byte_and_short_memory_opcodes():
+    """global_load_ubyte / sbyte / ushort / sshort and global_store_byte / short: the addressed bytes only (marks on
+    exactly those), zero- or sign-extended; inactive lanes touch nothing."""
+    import wave_emu as E
+    mem = E.Memory(track=True)
+    src = np.arange(256, dtype=np.uint8) * np.uint8(37) + np.uint8(0x7D)
+    base = mem.alloc(256, data=src)
+    dstb = mem.alloc(256)
+    wg = E.Workgroup(mem, [], {}, 64, 0, 0, 0)
+    w = wg.waves[0]
+    w.exec = EXEC
+
+    def run(text):
+        k = E.Insn(0, text)
+        wg.exec_insn(w, k, k.op, k.ops)
+
+    w.s[4], w.s[5] = base & M32, base >> 32
+    w.s[6], w.s[7] = dstb & M32, dstb >> 32
+    w.v[1] = np.arange(64, dtype=np.uint32) * np.uint32(3) + np.uint32(1)  # odd and even addresses
+    for op, nb, signed in (("ubyte", 1, False), ("sbyte", 1, True), ("ushort", 2, False), ("sshort", 2, True)):
+        w.v[0] = np.full(64, KEPT, np.uint32)
+        run("global_load_%s v0, v1, s[4:5] offset:2" % op)
+        for l in range(64):
+            at = 3 * l + 3
+            x = int.from_bytes(src[at:at + nb].tobytes(), "little")
+            if signed and x >> (8 * nb - 1):
+                x |= M32 & ~((1 << 8 * nb) - 1)
+            assert int(w.v[0][l]) == (x if EXEC >> l & 1 else KEPT), (op, l)
+    rd = mem.touched(base)[1]
+    want = np.zeros(256, bool)
+    for l in range(64):
+        if EXEC >> l & 1:
+            want[3 * l + 3:3 * l + 5] = True
+    assert np.array_equal(rd, want)
+    w.v[2] = np.arange(64, dtype=np.uint32) * np.uint32(0x01020304) + np.uint32(0xFFFEFDFC)
+    run("global_store_byte v1, v2, s[6:7]")
+    run("global_store_short v1, v2, s[6:7] offset:1")
+    out, wr = mem.view(dstb, 256), mem.touched(dstb)[2]
+    for l in range(64):
+        at, x = 3 * l + 1, int(w.v[2][l])
+        if EXEC >> l & 1:
+            assert (int(out[at]), int(out[at + 1]) | int(out[at + 2]) << 8) == (x & 0xFF, x & 0xFFFF), l
+            assert wr[at:at + 3].all()
+        else:
+            assert not wr[at:at + 3].any() and not out[at:at + 3].any(), l
+
+
+def test_scratch_marks_record_uninitialised_reads():
+    """Memory.declare_scratch: a read of a scratch byte no emulated store has written is recorded with its address and
+    the instruction's line; reads of stored bytes, and of regions not declared, are not.  Off by default."""
+    import wave_emu as E
+    mem = E.Memory()
+    a, b = mem.alloc(64, data=np.full(64, 0xA5, np.uint8)), mem.alloc(64)
+    mem.read(a, 8)
+    assert mem.scratch is None and mem.uninit == []
+    mem.declare_scratch(a)
+    mem.line = 17
+    mem.write(a + 8, bytes(8))
+    mem.read(a + 8, 8)
+    mem.read(b, 8)
+    assert mem.uninit == []
+    mem.read(a + 12, 8)  # four stored bytes, four stale ones
+    assert mem.uninit == [(a + 12, 8, 17)]
+    mem.view(a, 64)[:] = 0  # the harness's own access initialises nothing
+    mem.read(a, 1)
+    assert mem.uninit[-1] == (a, 1, 17)

@@ -20,8 +20,9 @@ window run, with their descriptor look-ahead and their staging of the following 
     would pass a test of addresses alone).
 
 The verify form runs as the captured form (verdict slots), so no arrival count depends on the grid.  Of the support
-kernels that read caller memory, sst_verify_prep_kernel runs the same way; verify_slots_reduce_kernel does not: its
-LDS reduction compiles to ds_read2_b64 / ds_read2st64_b64 / ds_write2st64_b64, which the emulator does not execute.
+kernels that read caller memory, sst_verify_prep_kernel and verify_slots_reduce_kernel run the same way (the latter's
+LDS reduction compiles to ds_read2_b64 / ds_read2st64_b64 / ds_write2st64_b64, which the emulator executes now).  The
+layout, log and list kernels have the same check in tests/test_isa_envelope_framing.py.
 """
 import os
 import re
@@ -338,3 +339,39 @@ def test_sst_verify_prep(env, skew):
     assert not wr.any()
     for base, (_, wmarks) in mem.marks.items():
         assert wmarks.all() if base in (d_len1, d_stored) else not wmarks.any(), "write at region 0x%x" % base
+
+
+REDUCE = "_ZN5kvsep26verify_slots_reduce_kernelEPKyjPyS2_"
+
+
+@pytest.mark.parametrize("n", [0, 1, 255, 256, 257, 700])
+@pytest.mark.parametrize("clean", [False, True])
+def test_verify_slots_reduce(env, n, clean):
+    """The captured verify call's verdict: the lowest bad block and the total over n (lowest, count) slots, one workgroup
+    of 256.  vslot is a region of exactly n pairs (n = 0: an unmapped address) and is read in full and never written;
+    the two verdict words are written in full.  A slot with count 0 holds the sentinel pair's "none" as its block."""
+    E, _, _ = env
+    rng = np.random.default_rng(n)
+    slot = np.zeros((n, 2), np.uint64)
+    slot[:, 0] = ~np.uint64(0)
+    if not clean and n:
+        hit = np.unique(np.concatenate([[0, n - 1], rng.integers(0, n, 5)]))
+        slot[hit, 0] = rng.integers(1 << 33, 1 << 40, hit.size).astype(np.uint64)
+        slot[hit, 1] = rng.integers(1, 1000, hit.size).astype(np.uint64)
+    mem = E.Memory(track=True)
+    d_slot = mem.alloc(16 * n, data=slot) if n else 1 << 40
+    d_fb = mem.alloc(8, data=np.array([E.SENTINEL], np.uint64))
+    d_nb = mem.alloc(8, data=np.array([E.SENTINEL], np.uint64))
+    try:
+        steps = E.launch_args(mem, ASM, REDUCE, 256, E.args_kernarg(ASM, REDUCE, [d_slot, n, d_fb, d_nb]), 1)
+    except E.EmuError as e:
+        raise AssertionError("verify_slots_reduce n %d: %s (vslot at 0x%x, %d bytes)" % (n, e, d_slot, 16 * n)) from e
+    print("verify_slots_reduce n %d: %d wave-instructions" % (n, steps))
+    total = int(slot[:, 1].sum())
+    assert mem.peek64(d_nb) == total
+    assert mem.peek64(d_fb) == (int(slot[:, 0].min()) if total else (1 << 64) - 1)
+    for base, (rd, wr) in mem.marks.items():
+        if base == d_slot:
+            assert rd.all() and not wr.any()
+        elif base in (d_fb, d_nb):
+            assert wr.all() and not rd.any()
