@@ -44,7 +44,8 @@ extern "C" {
  * kvsep_vlog_frame_auto_device) and the device log / MANIFEST reader (kvsep_log_walk_device,
  * kvsep_log_accept_gaps_device, kvsep_log_read_device) and its record assembly (kvsep_log_chains,
  * kvsep_log_chains_device, kvsep_log_records_device) and the device log / MANIFEST writer (kvsep_log_frame_layout,
- * kvsep_log_frame_device).
+ * kvsep_log_frame_device) and the SST table reader (kvsep_sst_footer, kvsep_sst_index_walk, kvsep_sst_index_device,
+ * kvsep_sst_table_verify_device, the KVSEP_SST_* status codes).
  * The reference's C++ symbol leveldb::crc32c::Extend is not in this library: it is in the libkvsep_leveldb_abi.so
  * shim. */
 #define KVSEP_ABI_VERSION 4
@@ -579,6 +580,78 @@ int kvsep_sst_verify_host(kvsep_crc32c_ctx* ctx, const char* file, uint64_t n, c
 int kvsep_sst_verify_list_host(kvsep_crc32c_ctx* ctx, const char* file, uint64_t n, const uint64_t* off,
                                const uint64_t* len, uint32_t* out, uint64_t* first_bad, uint64_t* nbad,
                                uint64_t* bad_idx, uint64_t bad_cap, uint64_t count);
+
+/* ---------------------------------------------------------------- SST table reader: footer, index walk, whole table
+ * Where the block handles of the forms above come from: the footer (Footer::DecodeFrom, table/format.cc:37-60) and the
+ * walk of the index block (Block::Block, DecodeEntry, Block::Iter, table/block.cc; BlockHandle::DecodeFrom), on the
+ * host and for a table image that is on the device, so that a device-resident table goes from bytes to a per-block
+ * verdict list on one stream with no host step.  ABI 4 gained them as new entry points and defines only.
+ *
+ * The status word of every form holds one of: */
+#define KVSEP_SST_OK 0
+#define KVSEP_SST_BAD_FOOTER 1       /* n < 48, wrong magic, a varint that leaves the 40 bytes, an unusable handle */
+#define KVSEP_SST_INDEX_CHECKSUM 2   /* table form: the index block failed its read check; no handle of it is trusted */
+#define KVSEP_SST_INDEX_COMPRESSED 3 /* table form: the index block's type byte is not 0 (Snappy is not rebuilt here) */
+#define KVSEP_SST_BAD_RESTARTS 4     /* block shorter than 4, restart count too large for it (or for the reserved
+                                        scratch), restart[0] != 0, a restart not above the one before or not below
+                                        the restart array */
+#define KVSEP_SST_BAD_ENTRY 5        /* an entry header that does not decode or leaves its restart run, shared != 0 on
+                                        a run's first entry, shared above the previous key's length */
+#define KVSEP_SST_BAD_HANDLE 6       /* an entry's value does not hold two varint64 */
+#define KVSEP_SST_CAP 7              /* table form: *nblocks + 2 > cap, the slots do not hold every block */
+/* A handle (off, len) is usable in an image of n bytes iff off + len + 5 <= n (no sum wraps): the block and its 5-byte
+ * trailer lie inside.
+ * First error wins: the result is the entries of all restart runs before the lowest run with an error, plus that run's
+ * entries before its error, in order; status is that error's code and *nblocks counts exactly those entries.  A run
+ * whose next restart is bad is walked to the end of the entries.  On a block with no error the result is what
+ * Block::Iter yields from SeekToFirst to the end.  A decoded handle that is not usable is still emitted; whether it may
+ * be dereferenced is decided where it is used. */
+/* The footer of an image of n bytes: handles = {meta_off, meta_len, index_off, index_len}, all 0 unless *status is
+ * KVSEP_SST_OK.  Host memory; returns KVSEP_EINVAL for a null pointer (file may be null when n == 0). */
+int kvsep_sst_footer(const char* file, uint64_t n, uint64_t handles[4], uint32_t* status);
+/* The walk of one index block's contents blk[0, blk_len) (without its trailer).  off / len (nullable when cap == 0) are
+ * written for exactly cap elements, zero from min(*nblocks, cap) on; *nblocks is the full count even when cap cut the
+ * arrays (status stays what the walk found).  Host memory. */
+int kvsep_sst_index_walk(const char* blk, uint64_t blk_len, uint64_t* off, uint64_t* len, uint64_t cap,
+                         uint64_t* nblocks, uint32_t* status);
+/* The device forms.  Every pointer except ctx is DEVICE memory; nothing is read back; asynchronous on `stream`; results
+ * are identical from run to run (no atomics).  The argument refusals come before the context or any device is touched:
+ * a null file_base with n != 0, a null required pointer, cap > 2^32 - 1, cap < 2 in the table form -- each KVSEP_EINVAL.
+ * A lane walks a restart run, so the reference's index blocks (block_restart_interval = 1) walk fully in parallel; one
+ * run of very many entries is one lane's chain of dependent loads.
+ * Scratch: two words per restart run (and one per 256 of them) plus the offsets pass's, and the SST arrays for cap.
+ * The restart count is device data, so the walk handles as many runs as its scratch holds: the largest count given to
+ * kvsep_crc32c_reserve, or cap when that is more (an eager call allocates for it; a captured call over the reservation
+ * fails with KVSEP_EINVAL before anything is enqueued).  A block with more runs than that stops with
+ * KVSEP_SST_BAD_RESTARTS and *nblocks = 0; nothing is written past the scratch.
+ * kvsep_crc32c_reserve(ctx, count >= max(cap, index_len / 4), total_bytes >= n) makes a call allocation-free and
+ * capturable, and is the sizing to use: index_len / 4 bounds the restart count of that block, and cap alone is enough
+ * for a table whose blocks all fit the slots at restart interval 1.  Without any knowledge of the table count = n / 4
+ * is always enough, but reserve sizes every per-block array of the library for count (on the order of 100 bytes a
+ * block: several GiB for a 258 MiB image).  A call launches lanes for the runs its scratch holds, never for more than
+ * n / 4.
+ * Memory touched: the image is never written; it is read bytewise, in the last 48 bytes, inside
+ * [index_off, index_off + index_len + 5) and, in the table form, at the blocks and trailers of usable handles -- so
+ * every read lies inside [file_base, file_base + n). */
+/* The walk alone.  handle[0..2) = index_off, index_len (an unusable one gives KVSEP_SST_BAD_FOOTER); off / len / cap /
+ * *nblocks / *status as kvsep_sst_index_walk gives them for the block's bytes. */
+int kvsep_sst_index_device(kvsep_crc32c_ctx* ctx, void* stream, const void* file_base, uint64_t n,
+                           const uint64_t* handle, uint64_t* off, uint64_t* len, uint64_t cap, uint64_t* nblocks,
+                           uint32_t* status);
+/* The whole table: the footer (handles[4], as kvsep_sst_footer), the read check of the index block alone, its walk,
+ * then the read check and list pass of kvsep_sst_verify_list_device over all cap >= 2 slots: crc / first_bad / nbad /
+ * bad_idx / bad_cap / ok as there, with count = cap.  Slots [0, m) are the data blocks in index order, m =
+ * min(*nblocks, cap - 2); slot m is the metaindex block, slot m + 1 the index block; the rest is padding (off = len = 0,
+ * checked as a block of length 0 that passes: ok = 1, not counted in *nbad).  *nblocks + 2 > cap sets KVSEP_SST_CAP.
+ * An index block that fails its checksum gives KVSEP_SST_INDEX_CHECKSUM, one whose type byte is not 0
+ * KVSEP_SST_INDEX_COMPRESSED (its checksum still reported): *nblocks = 0 and the list holds the metaindex and index
+ * blocks only.  A bad footer lists nothing.  Data blocks may be compressed: the check covers the stored bytes and the
+ * type byte.  An emitted handle that is not usable is reported bad (crc = 0) and never dereferenced.  max_len_hint: the
+ * longest block (0 = unknown), a hint only.  off / len / crc / ok go to kvsep_sst_salvage_device as they are. */
+int kvsep_sst_table_verify_device(kvsep_crc32c_ctx* ctx, void* stream, const void* file_base, uint64_t n, uint64_t* off,
+                                  uint64_t* len, uint32_t* crc, uint64_t* first_bad, uint64_t* nbad, uint64_t* bad_idx,
+                                  uint64_t bad_cap, uint8_t* ok, uint64_t cap, uint64_t max_len_hint,
+                                  uint64_t* nblocks, uint64_t* handles, uint32_t* status);
 
 /* ---------------------------------------------------------------- several GPUs in one process
  * Blocks are independent, so a batch is cut into contiguous block ranges balanced by bytes and each range runs on

@@ -53,6 +53,7 @@
 #include "log_run.h"
 #include "chain_run.h"
 #include "logw_run.h"
+#include "sst_run.h"
 
 namespace kvsep {
 
@@ -67,6 +68,7 @@ namespace kvsep {
 #include "crc32c_logwalk.inc"  // log_*_kernel: the log / MANIFEST walk and accept rule, a lane per 32 KiB block
 #include "crc32c_logchain.inc" // chain_*_kernel: the chains pass, FIRST / MIDDLE / LAST fragments into records
 #include "crc32c_logframe.inc" // logw_*_kernel: the log / MANIFEST write side, records into fragments and pads
+#include "crc32c_sstindex.inc" // sst_*_kernel: the SST footer, the index-block walk, the table form's slots
 
 }  // namespace kvsep
 
@@ -327,6 +329,21 @@ int ensure_logw(Scratch& sc, uint64_t n, bool capturing = false) {
   KVSEP_HIP(hipMalloc(&sc.d_logw_rec, (n ? n : 1) * 4));
   KVSEP_HIP(hipMalloc(&sc.d_logw_seed, (n ? n : 1) * 4));
   sc.cap_logw = n;
+  return KVSEP_OK;
+}
+
+// The SST index walk's words (crc32c_sstindex.inc): sst::scratch_words for the restart runs it is sized for.
+int ensure_sstidx(Scratch& sc, uint64_t runs, bool capturing = false) {
+  if (runs <= sc.cap_sstidx && sc.d_sstidx) return KVSEP_OK;
+  if (capturing)
+    return set_err(KVSEP_EINVAL, "a captured SST index walk larger than kvsep_crc32c_reserve sized its capture set for");
+  int rc = quiesce(sc);
+  if (rc) return rc;
+  hipFree(sc.d_sstidx);
+  sc.d_sstidx = nullptr;
+  sc.cap_sstidx = 0;
+  KVSEP_HIP(hipMalloc(&sc.d_sstidx, sst::scratch_words(runs) * 8));
+  sc.cap_sstidx = runs;
   return KVSEP_OK;
 }
 
@@ -818,6 +835,7 @@ void free_scratch(Scratch& sc) {
   hipFree(sc.d_chain);
   hipFree(sc.d_logw_rec);
   hipFree(sc.d_logw_seed);
+  hipFree(sc.d_sstidx);
   if (sc.last_use) (void)hipEventDestroy(sc.last_use);
   sc = Scratch();
 }
@@ -952,6 +970,8 @@ int reserve_scratch(kvsep_crc32c_ctx* c, Scratch& sc, uint64_t count, uint64_t t
   rc = ensure_chain(sc, count);
   if (rc) return rc;
   rc = ensure_logw(sc, count);
+  if (rc) return rc;
+  rc = ensure_sstidx(sc, sst::runs_for(sst::runs_reserved(count), 0));
   if (rc) return rc;
   return ensure_plan(sc, count, plan::pieces_reserved(c->piece_bytes, c->piece_auto, c->num_cus, count, total_bytes));
 }
@@ -1706,6 +1726,182 @@ int kvsep_log_read_device(kvsep_crc32c_ctx* c, void* stream, const void* base, u
     if (!r) r = launch_log_accept_in(sc, s, acc);
     return r;
   });
+}
+
+}  // extern "C"
+
+namespace {
+// ---- the SST table reader on the device (crc32c_sstindex.inc)
+
+static_assert(sst::kOk == KVSEP_SST_OK && sst::kBadFooter == KVSEP_SST_BAD_FOOTER &&
+                  sst::kIndexChecksum == KVSEP_SST_INDEX_CHECKSUM &&
+                  sst::kIndexCompressed == KVSEP_SST_INDEX_COMPRESSED && sst::kBadRestarts == KVSEP_SST_BAD_RESTARTS &&
+                  sst::kBadEntry == KVSEP_SST_BAD_ENTRY && sst::kBadHandle == KVSEP_SST_BAD_HANDLE &&
+                  sst::kCap == KVSEP_SST_CAP,
+              "sst_run.h restates the public status codes");
+static_assert(sst::kSkip == offsets::kSkip && sst::kNone == offsets::kKeepAll, "the walk reads the offsets pass's marks");
+
+struct SstWalkCall {
+  const void* base;
+  uint64_t n;
+  const uint64_t* handle;   // device: index_off, index_len
+  const uint64_t* handles;  // the table form: the footer's four (null: the walk alone)
+  const uint32_t* crc;      // ... the index block's checksum as computed
+  uint64_t* off;
+  uint64_t* len;
+  uint64_t cap;
+  uint64_t* nblocks;
+  uint32_t* status;
+};
+
+// The scratch of an SST walk on `s`, checked to hold a walk with `cap` slots (and the offsets pass over its runs):
+// refuses a captured call that was not reserved for before anything is enqueued, and allocates for an eager one.
+int sst_scratch(kvsep_crc32c_ctx* c, hipStream_t s, uint64_t n, uint64_t cap, bool* capturing, Scratch** psc) {
+  int rc = stream_scratch(c, s, c->sc, capturing, psc);
+  if (rc) return rc;
+  Scratch& sc = **psc;
+  rc = ensure_sstidx(sc, sst::runs_for(sc.cap_sstidx, cap), *capturing);
+  if (!rc) rc = ensure_offsets(sc, sst::runs_used(sc.cap_sstidx, n), *capturing);
+  return rc;
+}
+
+// The walk on a scratch the caller has acquired and sized: count, stop, the offsets pass over the counts, fill.
+int launch_sst_walk_in(Scratch& sc, hipStream_t s, const SstWalkCall& w) {
+  const uint64_t runs = sst::runs_used(sc.cap_sstidx, w.n);  // sst_scratch made cap_sstidx >= 1
+  SstIndexArgs a{};
+  a.img = static_cast<const uint8_t*>(w.base);
+  a.n = w.n;
+  a.handle = w.handle;
+  a.runs = runs;
+  a.handles = w.handles;
+  a.crc = w.crc;
+  a.stored = sc.d_sst_stored;
+  a.off = w.off, a.len = w.len, a.cap = w.cap;
+  a.nblocks = reinterpret_cast<unsigned long long*>(w.nblocks);
+  a.status = w.status;
+  a.stop = sc.d_sstidx;
+  a.cnt = sc.d_sstidx + sst::kStopWords;
+  a.errbase = a.cnt + runs;
+  a.wgstop = a.errbase + runs;
+  const uint64_t nwg = sst::grid_for(runs);
+  sst_index_count_kernel<<<unsigned(nwg), sst::kThreads, 0, s>>>(a);
+  KVSEP_HIP(hipGetLastError());
+  sst_index_stop_kernel<<<1, sst::kThreads, 0, s>>>(a.wgstop, nwg, a.errbase, a.stop);
+  KVSEP_HIP(hipGetLastError());
+  // base[r] = the entries before run r, *nblocks = all of them: run r is "segment" r of cnt[], kept up to the stop
+  int rc = launch_offsets_in(sc, s,
+                             OffsetsCall{reinterpret_cast<const uint64_t*>(a.cnt), nullptr, nullptr,
+                                         reinterpret_cast<const uint64_t*>(a.stop), 0, 0, 0, ~uint64_t(0),
+                                         reinterpret_cast<uint64_t*>(a.errbase), w.nblocks, nullptr, runs, runs});
+  if (rc) return rc;
+  sst_index_fill_kernel<<<unsigned(sst::pad_grid(runs, w.cap)), sst::kThreads, 0, s>>>(a);
+  KVSEP_HIP(hipGetLastError());
+  return KVSEP_OK;
+}
+
+// Refusals before the context or a device is touched.
+int sst_walk_args(const char* who, const void* base, uint64_t n, const void* off, const void* len, uint64_t cap,
+                  const void* nblocks, const void* status) {
+  const char* what = !base && n                  ? "null file_base with n != 0"
+                     : cap && (!off || !len)     ? "null off or len with cap != 0"
+                     : !nblocks || !status       ? "null nblocks or status"
+                     : cap > 0xffffffffull       ? "cap over 2^32 - 1"
+                                                 : nullptr;
+  if (!what) return KVSEP_OK;
+  return set_err(KVSEP_EINVAL, (std::string(who) + ": " + what).c_str());
+}
+}  // namespace
+
+extern "C" {
+
+int kvsep_sst_index_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, uint64_t n, const uint64_t* handle,
+                           uint64_t* off, uint64_t* len, uint64_t cap, uint64_t* nblocks, uint32_t* status) {
+  const char* who = "kvsep_sst_index_device";
+  int rc = sst_walk_args(who, file_base, n, off, len, cap, nblocks, status);
+  if (rc) return rc;
+  if (!handle) return set_err(KVSEP_EINVAL, "kvsep_sst_index_device: null handle");
+  if (!c) return set_err(KVSEP_EINVAL, "kvsep_sst_index_device: null ctx");
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard dg(c->device);
+  KVSEP_HIP(dg.err);
+  bool capturing = false;
+  Scratch* psc = nullptr;
+  rc = sst_scratch(c, s, n, cap, &capturing, &psc);
+  if (rc) return rc;
+  Scratch& sc = *psc;
+  rc = capturing ? KVSEP_OK : acquire(sc, s);
+  if (rc) return rc;
+  rc = launch_sst_walk_in(sc, s, SstWalkCall{file_base, n, handle, nullptr, nullptr, off, len, cap, nblocks, status});
+  if (rc) {
+    if (!capturing) (void)release(sc, s);
+    return rc;
+  }
+  return capturing ? KVSEP_OK : release(sc, s);
+}
+
+int kvsep_sst_table_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, uint64_t n, uint64_t* off,
+                                  uint64_t* len, uint32_t* crc, uint64_t* first_bad, uint64_t* nbad, uint64_t* bad_idx,
+                                  uint64_t bad_cap, uint8_t* ok, uint64_t cap, uint64_t max_len_hint, uint64_t* nblocks,
+                                  uint64_t* handles, uint32_t* status) {
+  const char* who = "kvsep_sst_table_verify_device";
+  if (cap < 2) return set_err(KVSEP_EINVAL, "kvsep_sst_table_verify_device: cap below 2 (the metaindex and index slots)");
+  int rc = sst_walk_args(who, file_base, n, off, len, cap, nblocks, status);
+  if (rc) return rc;
+  if (!crc || !handles) return set_err(KVSEP_EINVAL, "kvsep_sst_table_verify_device: null crc or handles");
+  if (!bad_idx && bad_cap) return set_err(KVSEP_EINVAL, "kvsep_sst_table_verify_device: null bad_idx with bad_cap > 0");
+  if (!c) return set_err(KVSEP_EINVAL, "kvsep_sst_table_verify_device: null ctx");
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard dg(c->device);
+  KVSEP_HIP(dg.err);
+  bool capturing = false;
+  Scratch* psc = nullptr;
+  rc = sst_scratch(c, s, n, cap, &capturing, &psc);
+  if (rc) return rc;
+  Scratch& sc = *psc;
+  // everything the two read checks and the list pass need, refused here rather than between two enqueued steps
+  const uint64_t hint1 = max_len_hint ? max_len_hint + 1 : 0;
+  rc = ensure_sst(sc, cap, capturing);
+  if (!rc && bad_cap) rc = ensure_list(sc, cap, capturing);
+  if (rc) return rc;
+  if (capturing && (!sc.d_verify || !sc.d_counter || sc.cap_vslot < vslots_needed(c)))
+    return set_err(KVSEP_EINVAL, "verify under capture needs kvsep_crc32c_reserve first");
+  const Route r_index = route_batch(c, 1, n, 0), r_all = route_batch(c, cap, n + cap, hint1);
+  if (r_index.planned) rc = ensure_plan(sc, 1, plan::pieces_needed(r_index.piece_bytes, 1, n), capturing);
+  if (!rc && r_all.planned) rc = ensure_plan(sc, cap, plan::pieces_needed(r_all.piece_bytes, cap, n + cap), capturing);
+  if (rc) return rc;
+  rc = capturing ? KVSEP_OK : acquire(sc, s);
+  if (rc) return rc;
+  const auto* img = static_cast<const uint8_t*>(file_base);
+  rc = [&]() -> int {
+    sst_footer_kernel<<<1, sst::kFooterThreads, 0, s>>>(img, n, handles, status);
+    KVSEP_HIP(hipGetLastError());
+    // the read check of the index block alone: its checksum into crc[0], its stored word into the scratch
+    sst_table_prep_kernel<<<1, sst::kThreads, 0, s>>>(
+        SstPrepArgs{img, n, handles + 2, handles + 3, 1, nullptr, status, cap, sc.d_sst_len1, sc.d_sst_stored});
+    KVSEP_HIP(hipGetLastError());
+    int r = launch_batch_in(c, sc, s, capturing, file_base, handles + 2, sc.d_sst_len1, nullptr, nullptr, crc, nullptr,
+                            nullptr, 1, n, 0);
+    if (r) return r;
+    r = launch_sst_walk_in(sc, s, SstWalkCall{file_base, n, handles + 2, handles, crc, off, len, cap, nblocks, status});
+    if (r) return r;
+    // the read check and the list pass over all cap slots: padding has length 0 and passes
+    sst_table_prep_kernel<<<unsigned(sst::grid_for(cap)), sst::kThreads, 0, s>>>(
+        SstPrepArgs{img, n, off, len, cap, reinterpret_cast<const unsigned long long*>(nblocks), status, cap,
+                    sc.d_sst_len1, sc.d_sst_stored});
+    KVSEP_HIP(hipGetLastError());
+    r = launch_batch_in(c, sc, s, capturing, file_base, off, sc.d_sst_len1, nullptr, sc.d_sst_stored, crc, first_bad,
+                        nbad, cap, n + cap, hint1);
+    if (r) return r;
+    return launch_list(sc, s, capturing, crc, sc.d_sst_stored, verdict_nbad(sc, first_bad, nbad),
+                       ListOut{bad_idx, bad_cap, ok}, cap);
+  }();
+  if (rc) {
+    if (!capturing) (void)release(sc, s);
+    return rc;
+  }
+  return capturing ? KVSEP_OK : release(sc, s);
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 #include "../../include/kvsep_crc32c.h"
 #include "chain_run.h"
 #include "logw_run.h"
+#include "sst_run.h"
 
 namespace kvsep {
 // crc32c_host.cpp: copies dst[i] <- src[i] (n[i] bytes) on the context's copier threads.
@@ -338,6 +339,44 @@ int kvsep_sst_verify_host(kvsep_crc32c_ctx* ctx, const char* file, uint64_t n, c
   }
   if (first_bad) *first_bad = fb;
   if (nbad) *nbad = nb;
+  return KVSEP_OK;
+}
+
+int kvsep_sst_footer(const char* file, uint64_t n, uint64_t handles[4], uint32_t* status) {
+  if ((!file && n) || !handles || !status) return einval("kvsep_sst_footer: null argument");
+  const auto rd = [file](uint64_t p) { return uint8_t(file[p]); };
+  const kvsep::sst::Footer f = kvsep::sst::footer(rd, n);  // sst_run.h holds every rule
+  for (int k = 0; k < 4; ++k) handles[k] = f.h[k];
+  *status = f.status;
+  return KVSEP_OK;
+}
+
+int kvsep_sst_index_walk(const char* blk, uint64_t blk_len, uint64_t* off, uint64_t* len, uint64_t cap,
+                         uint64_t* nblocks, uint32_t* status) {
+  namespace sst = kvsep::sst;
+  if ((!blk && blk_len) || (cap && (!off || !len)) || !nblocks || !status)
+    return einval("kvsep_sst_index_walk: null argument");
+  const auto rd = [blk](uint64_t p) { return uint8_t(blk[p]); };
+  uint64_t total = 0;
+  uint32_t code = sst::kOk;
+  const sst::Tail t = sst::tail(rd, 0, blk_len);
+  if (!t.ok) code = sst::kBadRestarts;
+  for (uint64_t r = 0; !code && r < t.nrestarts; ++r) {  // the runs in order: the first error is the lowest run's
+    const sst::Run run = sst::run_of(rd, 0, t, r);
+    if (!run.ok) {
+      code = sst::kBadRestarts;
+      break;
+    }
+    const sst::Walked w = sst::walk_run(rd, 0, run, t.restart_offset, [&](uint64_t k, uint64_t o, uint64_t l) {
+      if (total + k < cap) off[total + k] = o, len[total + k] = l;
+      return true;
+    });
+    total += w.count;
+    code = w.status;
+  }
+  for (uint64_t i = sst::held(total, cap); i < cap; ++i) off[i] = len[i] = 0;
+  *nblocks = total;
+  *status = code;
   return KVSEP_OK;
 }
 

@@ -47,6 +47,10 @@ struct Scratch {
   uint32_t* d_logw_rec = nullptr;            // log write side: a word per record ...
   uint32_t* d_logw_seed = nullptr;           // ... and per fragment slot (crc32c_logframe.inc)
   uint64_t cap_logw = 0;                     // records / fragment slots both are sized for
+  // SST index walk (crc32c_sstindex.inc): [keep_before, stop], then per restart run [cnt | error, later base], then a
+  // word per workgroup of the count kernel (its lowest run with an error): sst::scratch_words(cap_sstidx) words
+  unsigned long long* d_sstidx = nullptr;
+  uint64_t cap_sstidx = 0;  // restart runs d_sstidx is sized for
   hipEvent_t last_use = nullptr;
   hipStream_t last_stream = nullptr;
   bool used = false;

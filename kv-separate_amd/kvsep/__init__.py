@@ -165,6 +165,14 @@ _SIGS = {
     "kvsep_sst_verify_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64]),
+    "kvsep_sst_footer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
+    "kvsep_sst_index_walk": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
+    "kvsep_sst_index_device": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 3 +
+                               [ctypes.c_uint64] + [ctypes.c_void_p] * 2),
+    "kvsep_sst_table_verify_device": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 6 +
+                                      [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64] +
+                                      [ctypes.c_void_p] * 3),
     "kvsep_sst_trailers_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_uint64]),
     "kvsep_sst_verify_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
@@ -462,6 +470,36 @@ class Context:
         _check(lib().kvsep_log_walk_device(self._h, _stream_handle(stream), _dptr(base), n, _dptr(off), _dptr(length),
                                            _dptr(stored), _dptr(type), cap, _dptr(nrec)), "kvsep_log_walk_device")
         return nrec
+
+    def sst_index_device(self, file_base, n, handle, off, length, nblocks, status, cap=None, stream=None):
+        """kvsep_sst_index_device: the walk of sst_index_walk over the index block handle (int64 device tensor:
+        index_off, index_len) names in the n-byte device image at file_base.  off / length (int64) are written for
+        exactly cap elements: the data blocks' handles first, zeros after them; nblocks (one-element int64) receives the
+        full count, status (one-element int32) a SST_* code."""
+        if cap is None:
+            cap = min(int(off.numel()), int(length.numel()))
+        _check(lib().kvsep_sst_index_device(self._h, _stream_handle(stream), _dptr(file_base), n, _dptr(handle),
+                                            _dptr(off), _dptr(length), cap, _dptr(nblocks), _dptr(status)),
+               "kvsep_sst_index_device")
+        return nblocks
+
+    def sst_table_verify_device(self, file_base, n, off, length, crc, ok, nblocks, handles, status, first_bad=None,
+                                nbad=None, bad_idx=None, bad_cap=None, cap=None, max_len_hint=0, stream=None):
+        """kvsep_sst_table_verify_device: footer, index walk and the read check of every block of the n-byte device
+        table image at file_base, on one stream.  off / length (int64), crc (int32) and ok (uint8, optional) have cap
+        slots: the data blocks in index order, the metaindex block, the index block, padding.  handles (4 int64), nblocks
+        (one int64) and status (one int32, a SST_* code) are device tensors; first_bad / nbad / bad_idx as in
+        sst_verify_list_device."""
+        if cap is None:
+            cap = min(int(off.numel()), int(length.numel()), int(crc.numel()))
+        if bad_cap is None:
+            bad_cap = int(bad_idx.numel()) if bad_idx is not None else 0
+        _check(lib().kvsep_sst_table_verify_device(self._h, _stream_handle(stream), _dptr(file_base), n, _dptr(off),
+                                                   _dptr(length), _dptr(crc), _dptr(first_bad), _dptr(nbad),
+                                                   _dptr(bad_idx), bad_cap, _dptr(ok), cap, max_len_hint,
+                                                   _dptr(nblocks), _dptr(handles), _dptr(status)),
+               "kvsep_sst_table_verify_device")
+        return status
 
     def log_accept_gaps_device(self, base, n, off, length, type, ok, nrec, accept, gap=None, dropped=None,
                                bad_length=None, cap=None, stream=None):
@@ -912,6 +950,37 @@ def log_walk(image):
     lib().kvsep_log_walk(p, keep.nbytes, off.ctypes.data_as(ctypes.c_void_p), ln.ctypes.data_as(ctypes.c_void_p),
                          st.ctypes.data_as(ctypes.c_void_p), ty.ctypes.data_as(ctypes.c_void_p), cnt)
     return off, ln, st, ty
+
+
+SST_OK, SST_BAD_FOOTER, SST_INDEX_CHECKSUM, SST_INDEX_COMPRESSED = 0, 1, 2, 3
+SST_BAD_RESTARTS, SST_BAD_ENTRY, SST_BAD_HANDLE, SST_CAP = 4, 5, 6, 7
+
+
+def sst_footer(image):
+    """Footer of an SST image (table/format.cc:37-60) -> ((meta_off, meta_len, index_off, index_len), status)."""
+    p, keep = _buf(image)
+    h = np.zeros(4, np.uint64)
+    st = ctypes.c_uint32()
+    _check(lib().kvsep_sst_footer(p, keep.nbytes, h.ctypes.data_as(ctypes.c_void_p), ctypes.byref(st)),
+           "kvsep_sst_footer")
+    return tuple(int(x) for x in h), st.value
+
+
+def sst_index_walk(block, cap=None):
+    """Walk of one index block's contents (table/block.cc) -> (off, len, nblocks, status).  With cap the arrays have cap
+    elements (zeros after the handles) and nblocks is still the full count; without it they hold every handle."""
+    p, keep = _buf(block)
+    vp = ctypes.c_void_p
+    nb, st = ctypes.c_uint64(), ctypes.c_uint32()
+    if cap is None:
+        _check(lib().kvsep_sst_index_walk(p, keep.nbytes, None, None, 0, ctypes.byref(nb), ctypes.byref(st)),
+               "kvsep_sst_index_walk")
+        cap = nb.value
+    off = np.zeros(max(cap, 1), np.uint64)
+    ln = np.zeros(max(cap, 1), np.uint64)
+    _check(lib().kvsep_sst_index_walk(p, keep.nbytes, off.ctypes.data_as(vp), ln.ctypes.data_as(vp), cap,
+                                      ctypes.byref(nb), ctypes.byref(st)), "kvsep_sst_index_walk")
+    return off[:cap], ln[:cap], nb.value, st.value
 
 
 def log_accept(off, ok, n: int):

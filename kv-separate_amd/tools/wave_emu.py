@@ -826,16 +826,21 @@ class Workgroup:
     def sdwa(self, w, k, op, o, act):
         """VOP1/VOP2 SDWA: select bytes/words of the sources, run the plain op on temporaries, place the result per
         dst_sel / dst_unused."""
-        if any(x.startswith('sext(') for x in o) or 'clamp' in k.mods:
+        sext = [x.startswith('sext(') for x in o]
+        if (any(sext) and not op.startswith('v_cmp_')) or 'clamp' in k.mods:
             raise EmuError('sdwa modifier ' + k.text)
         t0, t1, td = self.SDWA_TMP
         if op.startswith('v_cmp_'):  # VOPC SDWA: the destination is an SGPR pair / VCC
             m = re.match(r'v_cmp_(\w+)_([ui])(16|32)_sdwa$', op)
             if not m:
                 raise EmuError('sdwa compare ' + k.text)
-            wide = m.group(3) == '32'  # a 32-bit compare of the (zero-extended, no sext) selected fields
+            wide = m.group(3) == '32'  # a 32-bit compare of the selected fields, zero-extended unless sext(...)
             for i, (t, sel) in enumerate(zip(o[1:3], (k.mods.get('src0_sel'), k.mods.get('src1_sel')))):
-                w.v[(t0, t1)[i]] = sdwa_sel(w.vget(t), sel) & np.uint32(0xFFFFFFFF if wide else 0xFFFF)
+                f = sdwa_sel(w.vget(t[5:-1] if sext[1 + i] else t), sel)
+                if sext[1 + i] and sel not in (None, 'DWORD'):  # the field's top bit fills the bits above it
+                    bits = 16 if sel.startswith('WORD_') else 8
+                    f = (f ^ np.uint32(1 << (bits - 1))) - np.uint32(1 << (bits - 1))
+                w.v[(t0, t1)[i]] = f & np.uint32(0xFFFFFFFF if wide else 0xFFFF)
             plain = Insn(k.line, 'v_cmp_%s_%s32_e64 %s, v%d, v%d' % (m.group(1), m.group(2), o[0], t0, t1))
             if m.group(2) == 'i' and not wide:
                 for t in (t0, t1):
@@ -979,6 +984,10 @@ class Workgroup:
             return
         if base == 'v_add_u16':  # VOP2 16-bit: the sum modulo 2^16, the high half of the destination zero
             w.vset(o[0], (V(o[1]) + V(o[2])) & u(0xFFFF))
+            return
+        if base in ('v_lshlrev_b16', 'v_lshrrev_b16'):  # VOP2 16-bit: the low halves, the destination's high half zero
+            sh, x = V(o[1]) & u(15), V(o[2]) & u(0xFFFF)
+            w.vset(o[0], ((x << sh) if base == 'v_lshlrev_b16' else (x >> sh)) & u(0xFFFF))
             return
         if base == 'v_alignbyte_b32':
             a, b, sh = V(o[1]).astype(np.uint64), V(o[2]).astype(np.uint64), ((V(o[3]) & u(3)) * u(8)).astype(np.uint64)
