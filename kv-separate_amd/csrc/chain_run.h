@@ -137,5 +137,15 @@ KVSEP_HD uint64_t write_tiles(uint64_t cap) { return tile_count(cap + 1); }
 // chain_reclen_kernel's grid: a lane per chain.
 KVSEP_HD uint64_t reclen_grid(uint64_t cap) { return (cap + kThreads - 1) / kThreads; }
 
+// The pass's scratch words, one array: per tile of records its summary and what the scan hands it, then the two grand
+// totals.  A call over ntiles tiles slices it at tile_words(ntiles); an array that holds cap records has
+// scratch_words(cap) words.
+constexpr uint64_t kGrandWords = 2;
+struct TileWords {
+  uint64_t sum, in, grand;
+};
+KVSEP_HD TileWords tile_words(uint64_t ntiles) { return {0, ntiles, 2 * ntiles}; }
+KVSEP_HD uint64_t scratch_words(uint64_t cap) { return tile_words(tile_count(cap)).grand + kGrandWords; }
+
 }  // namespace chain
 }  // namespace kvsep

@@ -150,25 +150,63 @@ int upload_tables(kvsep_crc32c_ctx* c) {
   return KVSEP_OK;
 }
 
-void free_plan(Scratch& sc) {
-  hipFree(sc.d_counts); hipFree(sc.d_pstart); hipFree(sc.d_pblk); hipFree(sc.d_partial);
-  hipFree(sc.d_scan_tmp);
-  sc.d_counts = sc.d_pstart = nullptr;
-  sc.d_pblk = sc.d_partial = nullptr;
-  sc.d_scan_tmp = nullptr;
-  sc.cap_count = sc.cap_pieces = 0;
-  sc.scan_tmp_bytes = 0;
-}
-
 // Wait until the scratch's previous user (on whatever stream) is done with it -- before a realloc.
 int quiesce(Scratch& sc) {
   if (sc.used && sc.last_use) KVSEP_HIP(hipEventSynchronize(sc.last_use));
   return KVSEP_OK;
 }
+}  // namespace
+
+// ---- DevBuf (kvsep_internal.h): the one place a scratch array is allocated, freed or given a capacity
+template <typename T, bool kAlways, typename U>
+void kvsep::DevBuf<T, kAlways, U>::drop() {
+  hipFree(p);
+  hipFree(q);
+  p = nullptr;
+  q = nullptr;
+  cap = 0;
+}
+
+template <typename T, bool kAlways, typename U>
+int kvsep::DevBuf<T, kAlways, U>::alloc(uint64_t need, uint64_t np, uint64_t nq) {
+  hipError_t e = np ? hipMalloc(&p, np * sizeof(T)) : hipSuccess;
+  if (e == hipSuccess && nq) e = hipMalloc(&q, nq * sizeof(U));
+  if (e != hipSuccess) {
+    drop();
+    return set_err(KVSEP_EHIP, "hipMalloc of a scratch array", e);
+  }
+  cap = need;
+  return KVSEP_OK;
+}
+
+template <typename T, bool kAlways, typename U>
+int kvsep::DevBuf<T, kAlways, U>::ensure(Scratch& sc, uint64_t need, bool capturing, const char* what, uint64_t np,
+                                         uint64_t nq) {
+  if (holds(need)) return KVSEP_OK;
+  if (capturing) return set_err(KVSEP_EINVAL, what);
+  int rc = quiesce(sc);
+  if (rc) return rc;
+  drop();
+  return alloc(need, np, nq);
+}
+
+namespace {
+void free_plan(Scratch& sc) {
+  sc.plan_blocks.drop();
+  sc.plan_pieces.drop();
+  sc.scan_tmp.drop();
+}
+
+// The scratch's cross-stream event, made on first use (kvsep_crc32c_reserve makes it for capture sets).
+int ensure_event(Scratch& sc) {
+  if (!sc.last_use) KVSEP_HIP(hipEventCreateWithFlags(&sc.last_use, hipEventDisableTiming));
+  return KVSEP_OK;
+}
 
 // Order this call behind the scratch's previous user when it ran on another stream.
 int acquire(Scratch& sc, hipStream_t s) {
-  if (!sc.last_use) KVSEP_HIP(hipEventCreateWithFlags(&sc.last_use, hipEventDisableTiming));
+  int rc = ensure_event(sc);
+  if (rc) return rc;
   if (sc.used && sc.last_stream != s) KVSEP_HIP(hipStreamWaitEvent(s, sc.last_use, 0));
   return KVSEP_OK;
 }
@@ -187,15 +225,16 @@ int release(Scratch& sc, hipStream_t s) {
 // calls on one scratch are ordered one after another by its events, so one set serves them all; captured calls publish
 // through verdict slots instead (ensure_vslot), which hold no state from one call to the next.
 constexpr uint32_t kVaccSetWords = kVaccStride * (1 + kVaccShards);
-unsigned long long* vacc_set(Scratch& sc) { return sc.d_verify + kVaccStride; }
+unsigned long long* vacc_set(Scratch& sc) { return sc.verify.p + kVaccStride; }
 
 int ensure_verify(Scratch& sc) {
-  if (sc.d_verify) return KVSEP_OK;
+  if (sc.verify.p) return KVSEP_OK;
   std::vector<unsigned long long> init(kVaccStride + kVaccSetWords, 0ull);
   init[0] = ~0ull;             // default first_bad
   init[kVaccStride] = ~0ull;   // the set's vacc[0]
-  KVSEP_HIP(hipMalloc(&sc.d_verify, init.size() * 8));
-  KVSEP_HIP(hipMemcpy(sc.d_verify, init.data(), init.size() * 8, hipMemcpyHostToDevice));
+  int rc = sc.verify.alloc(init.size(), init.size());
+  if (rc) return rc;
+  KVSEP_HIP(hipMemcpy(sc.verify.p, init.data(), init.size() * 8, hipMemcpyHostToDevice));
   sc.vacc_dirty = false;
   return KVSEP_OK;
 }
@@ -203,14 +242,18 @@ int ensure_verify(Scratch& sc) {
 // Verdict slots of captured verify calls: one per workgroup of the CRC kernel (num_cus) and of the combine kernel.
 uint32_t vslots_needed(const kvsep_crc32c_ctx* c) { return uint32_t(c->num_cus) + kCombineMaxGrid; }
 
+// (Only kvsep_crc32c_reserve sizes them, on a scratch no call is using: no quiesce, no capture path.)
 int ensure_vslot(Scratch& sc, uint32_t n) {
-  if (sc.cap_vslot >= n) return KVSEP_OK;
-  hipFree(sc.d_vslot);
-  sc.d_vslot = nullptr;
-  sc.cap_vslot = 0;
-  KVSEP_HIP(hipMalloc(&sc.d_vslot, uint64_t(n) * 16));
-  sc.cap_vslot = n;
-  return KVSEP_OK;
+  if (sc.vslot.cap >= n) return KVSEP_OK;
+  sc.vslot.drop();
+  return sc.vslot.alloc(n, 2 * uint64_t(n));
+}
+
+// The work counter of the guided schedule: allocated once per scratch, never under capture.
+int ensure_counter(Scratch& sc, bool capturing = false) {
+  if (sc.counter.p) return KVSEP_OK;
+  if (capturing) return set_err(KVSEP_EINVAL, "graph capture needs kvsep_crc32c_reserve first");
+  return sc.counter.alloc(4, 4);
 }
 
 // Puts the eager accumulator set back in its reset state, in stream order (two memsets).  Needed after an eager call
@@ -226,125 +269,48 @@ int reset_vacc(Scratch& sc, hipStream_t s) {
   return KVSEP_OK;
 }
 
-// SST verify scratch (len + 1 and the stored trailer words per block).
+// What each form's arrays are sized for and by: the capacity in the form's own unit, the refusal of a captured call
+// that kvsep_crc32c_reserve did not size the capture set for, and the elements of each array.
 int ensure_sst(Scratch& sc, uint64_t count, bool capturing = false) {
-  if (count <= sc.cap_sst) return KVSEP_OK;
-  if (capturing) return set_err(KVSEP_EINVAL, "SST verify under capture needs kvsep_crc32c_reserve first");
-  int rc = quiesce(sc);
-  if (rc) return rc;
-  hipFree(sc.d_sst_len1);
-  hipFree(sc.d_sst_stored);
-  sc.d_sst_len1 = nullptr;
-  sc.d_sst_stored = nullptr;
-  sc.cap_sst = 0;
-  KVSEP_HIP(hipMalloc(&sc.d_sst_len1, count * 8));
-  KVSEP_HIP(hipMalloc(&sc.d_sst_stored, count * 4));
-  sc.cap_sst = count;
-  return KVSEP_OK;
+  return sc.sst.ensure(sc, count, capturing, "SST verify under capture needs kvsep_crc32c_reserve first", count, count);
 }
 
 // The list forms' tile arrays (crc32c_verdicts.inc): one total and one base per kListTile blocks.
 int ensure_list(Scratch& sc, uint64_t count, bool capturing = false) {
   const uint64_t nt = list_tile_count(count);
-  if (nt <= sc.cap_tiles) return KVSEP_OK;
-  if (capturing)
-    return set_err(KVSEP_EINVAL, "a captured list call larger than kvsep_crc32c_reserve sized its capture set for");
-  int rc = quiesce(sc);
-  if (rc) return rc;
-  hipFree(sc.d_tile_cnt);
-  hipFree(sc.d_tile_base);
-  sc.d_tile_cnt = nullptr;
-  sc.d_tile_base = nullptr;
-  sc.cap_tiles = 0;
-  KVSEP_HIP(hipMalloc(&sc.d_tile_cnt, nt * 4));
-  KVSEP_HIP(hipMalloc(&sc.d_tile_base, nt * 8));
-  sc.cap_tiles = nt;
-  return KVSEP_OK;
+  return sc.tiles.ensure(sc, nt, capturing,
+                         "a captured list call larger than kvsep_crc32c_reserve sized its capture set for", nt, nt);
 }
 
-// The offsets pass's arrays (crc32c_offsets.inc): one extent per block; per tile of offsets::kTile blocks a sum, a kept
-// count and a base, then the two grand totals.
 int ensure_offsets(Scratch& sc, uint64_t count, bool capturing = false) {
-  if (count <= sc.cap_off) return KVSEP_OK;
-  if (capturing)
-    return set_err(KVSEP_EINVAL, "a captured offsets pass larger than kvsep_crc32c_reserve sized its capture set for");
-  int rc = quiesce(sc);
-  if (rc) return rc;
-  hipFree(sc.d_off_ext);
-  hipFree(sc.d_off_tile);
-  sc.d_off_ext = nullptr;
-  sc.d_off_tile = nullptr;
-  sc.cap_off = 0;
-  KVSEP_HIP(hipMalloc(&sc.d_off_ext, count * 8));
-  KVSEP_HIP(hipMalloc(&sc.d_off_tile, (3 * offsets::tile_count(count) + 2) * 8));
-  sc.cap_off = count;
-  return KVSEP_OK;
+  return sc.off.ensure(sc, count, capturing,
+                       "a captured offsets pass larger than kvsep_crc32c_reserve sized its capture set for", count,
+                       offsets::scratch_words(count));
 }
 
-// The log reader's words (crc32c_logwalk.inc): seven per 32 KiB block of the image, then the stop index.
-constexpr uint64_t kLogWords = 7;
 int ensure_log(Scratch& sc, uint64_t nblocks, bool capturing = false) {
-  if (nblocks <= sc.cap_log && sc.d_log) return KVSEP_OK;
-  if (capturing)
-    return set_err(KVSEP_EINVAL, "a captured log read larger than kvsep_crc32c_reserve sized its capture set for");
-  int rc = quiesce(sc);
-  if (rc) return rc;
-  hipFree(sc.d_log);
-  sc.d_log = nullptr;
-  sc.cap_log = 0;
-  KVSEP_HIP(hipMalloc(&sc.d_log, (kLogWords * nblocks + 1) * 8));
-  sc.cap_log = nblocks;
-  return KVSEP_OK;
+  return sc.log.ensure(sc, nblocks, capturing,
+                       "a captured log read larger than kvsep_crc32c_reserve sized its capture set for",
+                       logrun::scratch_words(nblocks));
 }
 
-// The chains pass's words (crc32c_logchain.inc): per tile of chain::kTile records a summary and what the scan hands the
-// tile, then the two grand totals.
 int ensure_chain(Scratch& sc, uint64_t cap, bool capturing = false) {
-  if (cap <= sc.cap_chain && sc.d_chain) return KVSEP_OK;
-  if (capturing)
-    return set_err(KVSEP_EINVAL, "a captured chains pass larger than kvsep_crc32c_reserve sized its capture set for");
-  int rc = quiesce(sc);
-  if (rc) return rc;
-  hipFree(sc.d_chain);
-  sc.d_chain = nullptr;
-  sc.cap_chain = 0;
-  KVSEP_HIP(hipMalloc(&sc.d_chain, (2 * chain::tile_count(cap) + 2) * 8));
-  sc.cap_chain = cap;
-  return KVSEP_OK;
+  return sc.chain.ensure(sc, cap, capturing,
+                         "a captured chains pass larger than kvsep_crc32c_reserve sized its capture set for",
+                         chain::scratch_words(cap));
 }
 
-// The log write side's words (crc32c_logframe.inc): one per record (its block offset and pad count) and one per fragment
-// slot (the init of its checksum).
+// One word per record and one per fragment slot, one of each at least.
 int ensure_logw(Scratch& sc, uint64_t n, bool capturing = false) {
-  if (n <= sc.cap_logw && sc.d_logw_rec) return KVSEP_OK;
-  if (capturing)
-    return set_err(KVSEP_EINVAL, "a captured log frame larger than kvsep_crc32c_reserve sized its capture set for");
-  int rc = quiesce(sc);
-  if (rc) return rc;
-  hipFree(sc.d_logw_rec);
-  hipFree(sc.d_logw_seed);
-  sc.d_logw_rec = nullptr;
-  sc.d_logw_seed = nullptr;
-  sc.cap_logw = 0;
-  KVSEP_HIP(hipMalloc(&sc.d_logw_rec, (n ? n : 1) * 4));
-  KVSEP_HIP(hipMalloc(&sc.d_logw_seed, (n ? n : 1) * 4));
-  sc.cap_logw = n;
-  return KVSEP_OK;
+  return sc.logw.ensure(sc, n, capturing,
+                        "a captured log frame larger than kvsep_crc32c_reserve sized its capture set for", n ? n : 1,
+                        n ? n : 1);
 }
 
-// The SST index walk's words (crc32c_sstindex.inc): sst::scratch_words for the restart runs it is sized for.
 int ensure_sstidx(Scratch& sc, uint64_t runs, bool capturing = false) {
-  if (runs <= sc.cap_sstidx && sc.d_sstidx) return KVSEP_OK;
-  if (capturing)
-    return set_err(KVSEP_EINVAL, "a captured SST index walk larger than kvsep_crc32c_reserve sized its capture set for");
-  int rc = quiesce(sc);
-  if (rc) return rc;
-  hipFree(sc.d_sstidx);
-  sc.d_sstidx = nullptr;
-  sc.cap_sstidx = 0;
-  KVSEP_HIP(hipMalloc(&sc.d_sstidx, sst::scratch_words(runs) * 8));
-  sc.cap_sstidx = runs;
-  return KVSEP_OK;
+  return sc.sstidx.ensure(sc, runs, capturing,
+                          "a captured SST index walk larger than kvsep_crc32c_reserve sized its capture set for",
+                          sst::scratch_words(runs));
 }
 
 // What a list form adds to its verify call: bad_idx[0, min(nbad, bad_cap)) and / or ok[0, count).
@@ -366,12 +332,12 @@ int launch_list(Scratch& sc, hipStream_t s, bool capturing, const uint32_t* out,
     if (rc) return rc;
   }
   verdict_tile_count_kernel<<<unsigned(nt), kListThreads, 0, s>>>(out, stored, count, nb, l.ok,
-                                                         l.bad_cap ? sc.d_tile_cnt : nullptr);
+                                                         l.bad_cap ? sc.tiles.p : nullptr);
   KVSEP_HIP(hipGetLastError());
   if (!l.bad_cap) return KVSEP_OK;
-  verdict_tile_scan_kernel<<<1, kListThreads, 0, s>>>(sc.d_tile_cnt, sc.d_tile_base, uint32_t(nt), nb);
+  verdict_tile_scan_kernel<<<1, kListThreads, 0, s>>>(sc.tiles.p, sc.tiles.q, uint32_t(nt), nb);
   KVSEP_HIP(hipGetLastError());
-  verdict_scatter_kernel<<<unsigned(nt), kListThreads, 0, s>>>(out, stored, count, nb, sc.d_tile_base, l.bad_idx, l.bad_cap);
+  verdict_scatter_kernel<<<unsigned(nt), kListThreads, 0, s>>>(out, stored, count, nb, sc.tiles.q, l.bad_idx, l.bad_cap);
   KVSEP_HIP(hipGetLastError());
   return KVSEP_OK;
 }
@@ -379,7 +345,7 @@ int launch_list(Scratch& sc, hipStream_t s, bool capturing, const uint32_t* out,
 // Where a verify call put its count: the caller's word, or the scratch's own when the caller passed none
 // (launch_batch_body).
 const uint64_t* verdict_nbad(const Scratch& sc, const uint64_t* first_bad, const uint64_t* nbad) {
-  return first_bad && nbad ? nbad : reinterpret_cast<const uint64_t*>(sc.d_verify + 1);
+  return first_bad && nbad ? nbad : reinterpret_cast<const uint64_t*>(sc.verify.p + 1);
 }
 
 // Room for a plan of `count` blocks and `pieces` entries (plan_size.h: pieces_needed of a call, pieces_reserved of a
@@ -388,24 +354,23 @@ int ensure_plan(Scratch& sc, uint64_t count, uint64_t pieces, bool capturing = f
   // hipcub's scan takes an int item count; piece and block indices are u32 in the kernels
   if (count > 0x7fffffffull) return set_err(KVSEP_EINVAL, "more than 2^31 - 1 blocks in one batch that needs a plan");
   if (pieces > 0xffffffffull) return set_err(KVSEP_EINVAL, "batch too large for u32 piece indices");
-  if (count <= sc.cap_count && pieces <= sc.cap_pieces) return KVSEP_OK;
+  if (sc.plan_blocks.holds(count) && sc.plan_pieces.holds(pieces)) return KVSEP_OK;
   if (capturing)
     return set_err(KVSEP_EINVAL, "a captured planned batch larger than kvsep_crc32c_reserve sized its capture set for");
-  const uint64_t nc = std::max<uint64_t>(count, sc.cap_count), np = std::max<uint64_t>(pieces, sc.cap_pieces);
+  // both dimensions grow together, neither shrinks: the three buffers are dropped and allocated as one
+  const uint64_t nc = std::max(count, sc.plan_blocks.cap), np = std::max(pieces, sc.plan_pieces.cap);
   int rc = quiesce(sc);
   if (rc) return rc;
   free_plan(sc);
-  KVSEP_HIP(hipMalloc(&sc.d_counts, nc * 8));
-  KVSEP_HIP(hipMalloc(&sc.d_pstart, (nc + 1) * 8));
-  KVSEP_HIP(hipMalloc(&sc.d_pblk, np * 4));
-  KVSEP_HIP(hipMalloc(&sc.d_partial, np * 4));
+  rc = sc.plan_blocks.alloc(nc, nc, nc + 1);
+  if (!rc) rc = sc.plan_pieces.alloc(np, np, np);
   size_t tb = 0;
-  KVSEP_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb, sc.d_counts, sc.d_pstart + 1, int(nc), hipStream_t(0)));
-  KVSEP_HIP(hipMalloc(&sc.d_scan_tmp, tb));
-  sc.scan_tmp_bytes = tb;
-  sc.cap_count = nc;
-  sc.cap_pieces = np;
-  return KVSEP_OK;
+  if (!rc && hipcub::DeviceScan::InclusiveSum(nullptr, tb, sc.plan_blocks.p, sc.plan_blocks.q + 1, int(nc),
+                                              hipStream_t(0)) != hipSuccess)
+    rc = set_err(KVSEP_EHIP, "hipcub::DeviceScan::InclusiveSum (temporary storage query)");
+  if (!rc) rc = sc.scan_tmp.alloc(tb, tb);
+  if (rc) free_plan(sc);
+  return rc;
 }
 
 // Narrow or wide kernel for an unsplit batch (every block <= piece_bytes, known from the max_len hint)?  The
@@ -598,7 +563,59 @@ int stream_scratch(kvsep_crc32c_ctx* c, hipStream_t s, Scratch& eager, bool* cap
                                      "those graphs are destroyed");
 }
 
-// Every use of a Scratch is bracketed by acquire/release (event ordering across streams).
+// The scratch the calls on `s` run on, checked to hold what `needs(sc, capturing)` asks for: a captured call that was
+// not reserved for is refused and an eager one allocates, before anything is enqueued.  (A capture that claimed a set
+// keeps it when the needs refuse.)  The caller holds a DeviceGuard.
+template <typename Needs>
+int sized_scratch(kvsep_crc32c_ctx* c, hipStream_t s, Scratch& eager, Needs needs, bool* capturing, Scratch** psc) {
+  int rc = stream_scratch(c, s, eager, capturing, psc);
+  return rc ? rc : needs(**psc, *capturing);
+}
+
+// That check alone, for a composite call whose later steps bracket their own scratch: it refuses before its first step
+// enqueues anything.  The caller holds the context's mutex.
+template <typename Needs>
+int check_scratch(kvsep_crc32c_ctx* c, hipStream_t s, Needs needs) {
+  DeviceGuard dg(c->device);
+  KVSEP_HIP(dg.err);
+  bool capturing = false;
+  Scratch* psc = nullptr;
+  return sized_scratch(c, s, c->sc, needs, &capturing, &psc);
+}
+
+// Every use of a Scratch goes through this bracket.  Under stream capture (hipGraph) the call only
+// records its nodes, on its capture's own set (stream_scratch): the cross-stream scratch events are skipped (a captured
+// wait on an event recorded outside the capture is not allowed) and nothing is allocated -- kvsep_crc32c_reserve sized
+// the set.  Calls captured into one graph share its set, so they must be ordered within the graph (captured on one
+// stream, or joined).  An eager call sizes the scratch (`needs`), orders itself behind the scratch's previous user
+// (acquire), enqueues `body(sc, capturing)` and records the scratch's event (release) -- after a failed body too, so
+// that whatever it enqueued stays ordered before the scratch's next user.  The needs run before acquire: acquire only
+// creates the event and enqueues a wait on `s`, and a need that reallocates synchronises the host on that same event
+// (quiesce), so the order of the two makes no difference, and a refusal has enqueued nothing.  The caller holds the
+// context's mutex; `eager` is the context's scratch, or a staging slot's own.
+template <typename Needs, typename Body>
+int with_scratch(kvsep_crc32c_ctx* c, hipStream_t s, Scratch& eager, Needs needs, Body body) {
+  DeviceGuard dg(c->device);
+  KVSEP_HIP(dg.err);
+  bool capturing = false;
+  Scratch* psc = nullptr;
+  int rc = sized_scratch(c, s, eager, needs, &capturing, &psc);
+  if (!rc && !capturing) rc = acquire(*psc, s);
+  if (rc) return rc;
+  rc = body(*psc, capturing);
+  if (capturing) return rc;
+  const int rel = release(*psc, s);
+  return rc ? rc : rel;
+}
+
+// The plan of a checksum step inside a larger call, when its route takes one: sized with the call's other needs.
+int ensure_plan_for(kvsep_crc32c_ctx* c, Scratch& sc, uint64_t count, uint64_t total_bytes, uint64_t max_len,
+                    bool capturing) {
+  const Route r = route_batch(c, count, total_bytes, max_len);
+  if (!r.planned) return KVSEP_OK;
+  return ensure_plan(sc, count, plan::pieces_needed(r.piece_bytes, count, total_bytes), capturing);
+}
+
 int launch_batch(kvsep_crc32c_ctx* c, Scratch& eager, hipStream_t s, const void* base, const uint64_t* off,
                  const uint64_t* len, const uint32_t* init, const uint32_t* expect, uint32_t* out, uint64_t* first_bad,
                  uint64_t* nbad, uint64_t count, uint64_t total_bytes, uint64_t max_len,
@@ -606,31 +623,16 @@ int launch_batch(kvsep_crc32c_ctx* c, Scratch& eager, hipStream_t s, const void*
   if (!base || !off || !len || !out) return set_err(KVSEP_EINVAL, "null pointer argument");
   // block indices travel as u32 through the descriptor windows and the piece table
   if (count > 0xffffffffull) return set_err(KVSEP_EINVAL, "more than 2^32 - 1 blocks in one batch");
-  DeviceGuard dg(c->device);
-  KVSEP_HIP(dg.err);
-  // Under stream capture (hipGraph) the call only records its nodes, on its capture's own set (stream_scratch): the
-  // cross-stream scratch events are skipped (a captured wait on an event recorded outside the capture is not allowed)
-  // and nothing is allocated -- kvsep_crc32c_reserve sized the set.  Calls captured into one graph share its set, so
-  // they must be ordered within the graph (captured on one stream, or joined).
-  bool capturing = false;
-  Scratch* psc = nullptr;
-  int rc = stream_scratch(c, s, eager, &capturing, &psc);
-  if (rc) return rc;
-  Scratch& sc = *psc;
-  rc = capturing ? KVSEP_OK : acquire(sc, s);
-  if (rc) return rc;
-  if (list && list->bad_cap) {  // refused before anything is enqueued
-    rc = ensure_list(sc, count, capturing);
-    if (rc) return rc;
-  }
-  rc = launch_batch_in(c, sc, s, capturing, base, off, len, init, expect, out, first_bad, nbad, count, total_bytes,
-                       max_len);
-  if (!rc && list) rc = launch_list(sc, s, capturing, out, expect, verdict_nbad(sc, first_bad, nbad), *list, count);
-  if (rc) {
-    if (!capturing) (void)release(sc, s);  // whatever was enqueued stays ordered before the scratch's next user
-    return rc;
-  }
-  return capturing ? KVSEP_OK : release(sc, s);
+  return with_scratch(
+      c, s, eager,
+      [&](Scratch& sc, bool capturing) { return list && list->bad_cap ? ensure_list(sc, count, capturing) : KVSEP_OK; },
+      [&](Scratch& sc, bool capturing) {
+        int rc = launch_batch_in(c, sc, s, capturing, base, off, len, init, expect, out, first_bad, nbad, count,
+                                 total_bytes, max_len);
+        if (!rc && list)
+          rc = launch_list(sc, s, capturing, out, expect, verdict_nbad(sc, first_bad, nbad), *list, count);
+        return rc;
+      });
 }
 
 int launch_batch_body(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capturing, PiecesArgs& a,
@@ -645,9 +647,9 @@ int launch_batch_in(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool captur
   PiecesArgs a{};
   if (expect) {
     if (capturing) {  // verdict slots (reserved with the capture set), published by the reduce kernel
-      if (!sc.d_verify || sc.cap_vslot < vslots_needed(c))
+      if (!sc.verify.p || sc.vslot.cap < vslots_needed(c))
         return set_err(KVSEP_EINVAL, "verify under capture needs kvsep_crc32c_reserve first");
-      a.vslot = sc.d_vslot;
+      a.vslot = sc.vslot.p;
     } else {
       int rc = ensure_verify(sc);
       if (rc) return rc;
@@ -681,8 +683,8 @@ int launch_batch_body(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capt
   a.tabs = c->d_tabs;
   if (expect) {
     if (!first_bad || !nbad) {
-      first_bad = reinterpret_cast<uint64_t*>(sc.d_verify);
-      nbad = reinterpret_cast<uint64_t*>(sc.d_verify + 1);
+      first_bad = reinterpret_cast<uint64_t*>(sc.verify.p);
+      nbad = reinterpret_cast<uint64_t*>(sc.verify.p + 1);
     }
     if (count == 0) {  // nothing to check, no CRC kernel: the verdict is "none" (first_bad = ~0, nbad = 0)
       start_words_kernel<<<1, 64, 0, s>>>(nullptr, reinterpret_cast<unsigned long long*>(first_bad),
@@ -702,31 +704,31 @@ int launch_batch_body(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capt
   a.guided_div = 0;  // adaptive (crc32c_pieces_kernel)
   a.guided_cap = 0;
   if (dyn) {
-    if (!sc.d_counter && capturing) return set_err(KVSEP_EINVAL, "graph capture needs kvsep_crc32c_reserve first");
-    if (!sc.d_counter) KVSEP_HIP(hipMalloc(&sc.d_counter, 16));
-    a.work_counter = sc.d_counter;
+    int rc = ensure_counter(sc, capturing);
+    if (rc) return rc;
+    a.work_counter = sc.counter.p;
   }
   // The start-state words (pstart[0], the guided counter) are written by a kernel of the call, never by a memset node
   // (see crc32c_plan_count_kernel).
   if (planned) {
     int rc = ensure_plan(sc, count, plan::pieces_needed(a.piece_bytes, count, total_bytes), capturing);
     if (rc) return rc;
-    a.pstart = sc.d_pstart;
-    a.pblk = sc.d_pblk;
-    a.partial = sc.d_partial;
-    a.max_pieces = sc.cap_pieces;
+    a.pstart = sc.plan_blocks.q;
+    a.pblk = sc.plan_pieces.p;
+    a.partial = sc.plan_pieces.q;
+    a.max_pieces = sc.plan_pieces.cap;
     const unsigned nb = unsigned((count + 255) / 256);
-    crc32c_plan_count_kernel<<<nb, 256, 0, s>>>(len, count, a.piece_bytes, sc.d_counts, sc.d_pstart,
-                                                dyn ? sc.d_counter : nullptr);
+    crc32c_plan_count_kernel<<<nb, 256, 0, s>>>(len, count, a.piece_bytes, sc.plan_blocks.p, sc.plan_blocks.q,
+                                                dyn ? sc.counter.p : nullptr);
     KVSEP_HIP(hipGetLastError());
-    size_t tb = sc.scan_tmp_bytes;
-    KVSEP_HIP(hipcub::DeviceScan::InclusiveSum(sc.d_scan_tmp, tb, sc.d_counts, sc.d_pstart + 1, int(count), s));
-    crc32c_plan_expand_kernel<<<nb, 256, 0, s>>>(sc.d_pstart, count, sc.cap_pieces, sc.d_pblk);
+    size_t tb = sc.scan_tmp.cap;
+    KVSEP_HIP(hipcub::DeviceScan::InclusiveSum(sc.scan_tmp.p, tb, sc.plan_blocks.p, sc.plan_blocks.q + 1, int(count), s));
+    crc32c_plan_expand_kernel<<<nb, 256, 0, s>>>(sc.plan_blocks.q, count, sc.plan_pieces.cap, sc.plan_pieces.p);
     KVSEP_HIP(hipGetLastError());
   } else {
     a.max_pieces = count;
     if (dyn) {
-      start_words_kernel<<<1, 64, 0, s>>>(sc.d_counter, nullptr, nullptr);
+      start_words_kernel<<<1, 64, 0, s>>>(sc.counter.p, nullptr, nullptr);
       KVSEP_HIP(hipGetLastError());
     }
   }
@@ -821,21 +823,7 @@ int device_batch_locked(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, const v
 
 void free_scratch(Scratch& sc) {
   if (sc.used && sc.last_use) (void)hipEventSynchronize(sc.last_use);
-  free_plan(sc);
-  hipFree(sc.d_counter);
-  hipFree(sc.d_verify);
-  hipFree(sc.d_vslot);
-  hipFree(sc.d_sst_len1);
-  hipFree(sc.d_sst_stored);
-  hipFree(sc.d_tile_cnt);
-  hipFree(sc.d_tile_base);
-  hipFree(sc.d_off_ext);
-  hipFree(sc.d_off_tile);
-  hipFree(sc.d_log);
-  hipFree(sc.d_chain);
-  hipFree(sc.d_logw_rec);
-  hipFree(sc.d_logw_seed);
-  hipFree(sc.d_sstidx);
+  sc.each_buf([](auto& b) { b.drop(); });
   if (sc.last_use) (void)hipEventDestroy(sc.last_use);
   sc = Scratch();
 }
@@ -953,25 +941,17 @@ namespace {
 // worst of the piece sizes a smaller batch can pick, and for the SST read check's extra byte per block
 // (plan::pieces_reserved).
 int reserve_scratch(kvsep_crc32c_ctx* c, Scratch& sc, uint64_t count, uint64_t total_bytes) {
-  if (!sc.d_counter) KVSEP_HIP(hipMalloc(&sc.d_counter, 16));
-  int rc = ensure_verify(sc);
-  if (rc) return rc;
-  if (!sc.last_use) KVSEP_HIP(hipEventCreateWithFlags(&sc.last_use, hipEventDisableTiming));
-  rc = ensure_sst(sc, count);
-  if (rc) return rc;
-  rc = ensure_vslot(sc, vslots_needed(c));
-  if (rc) return rc;
-  rc = ensure_list(sc, count);
-  if (rc) return rc;
-  rc = ensure_offsets(sc, count);
-  if (rc) return rc;
-  rc = ensure_log(sc, count);
-  if (rc) return rc;
-  rc = ensure_chain(sc, count);
-  if (rc) return rc;
-  rc = ensure_logw(sc, count);
-  if (rc) return rc;
-  rc = ensure_sstidx(sc, sst::runs_for(sst::runs_reserved(count), 0));
+  int rc = ensure_counter(sc);
+  if (!rc) rc = ensure_verify(sc);
+  if (!rc) rc = ensure_event(sc);
+  if (!rc) rc = ensure_sst(sc, count);
+  if (!rc) rc = ensure_vslot(sc, vslots_needed(c));
+  if (!rc) rc = ensure_list(sc, count);
+  if (!rc) rc = ensure_offsets(sc, count);
+  if (!rc) rc = ensure_log(sc, count);
+  if (!rc) rc = ensure_chain(sc, count);
+  if (!rc) rc = ensure_logw(sc, count);
+  if (!rc) rc = ensure_sstidx(sc, sst::runs_for(sst::runs_reserved(count), 0));
   if (rc) return rc;
   return ensure_plan(sc, count, plan::pieces_reserved(c->piece_bytes, c->piece_auto, c->num_cus, count, total_bytes));
 }
@@ -1095,27 +1075,16 @@ int kvsep_log_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* base,
   if (count > 0xffffffffull) return set_err(KVSEP_EINVAL, "kvsep_log_verify_device: more than 2^32 - 1 records");
   std::lock_guard<std::mutex> g(c->mu);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  DeviceGuard dg(c->device);
-  KVSEP_HIP(dg.err);
-  bool capturing = false;
-  Scratch* psc = nullptr;
-  int rc = stream_scratch(c, s, c->sc, &capturing, &psc);
-  if (rc) return rc;
-  Scratch& sc = *psc;
-  rc = capturing ? KVSEP_OK : acquire(sc, s);
-  if (rc) return rc;
   // the CRCs go to the scratch's u32 word per block (the SST read check's array: kvsep_crc32c_reserve sizes it), then
   // ok[i] = Mask(crc) == stored[i], which is db/log_reader.cc:250-258's crc == Unmask(stored)
-  rc = ensure_sst(sc, count, capturing);
-  if (!rc)
-    rc = launch_batch_in(c, sc, s, capturing, base, off, len, nullptr, nullptr, sc.d_sst_stored, nullptr, nullptr,
-                         count, total_bytes, max_len);
-  if (!rc) rc = launch_list(sc, s, capturing, sc.d_sst_stored, stored, nullptr, ListOut{nullptr, 0, ok}, count);
-  if (rc) {
-    if (!capturing) (void)release(sc, s);
-    return rc;
-  }
-  return capturing ? KVSEP_OK : release(sc, s);
+  return with_scratch(
+      c, s, c->sc, [&](Scratch& sc, bool capturing) { return ensure_sst(sc, count, capturing); },
+      [&](Scratch& sc, bool capturing) {
+        int rc = launch_batch_in(c, sc, s, capturing, base, off, len, nullptr, nullptr, sc.sst.q, nullptr, nullptr,
+                                 count, total_bytes, max_len);
+        if (!rc) rc = launch_list(sc, s, capturing, sc.sst.q, stored, nullptr, ListOut{nullptr, 0, ok}, count);
+        return rc;
+      });
 }
 
 int kvsep_fill_splitmix64_device(void* stream, void* dst, uint64_t nbytes, uint64_t seed, uint64_t stream_offset) {
@@ -1300,37 +1269,25 @@ int sst_verify_locked(kvsep_crc32c_ctx* c, void* stream, const void* file_base, 
                       const uint64_t* len, uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint64_t count,
                       uint64_t total_bytes, uint64_t max_len, const ListOut* list) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  DeviceGuard dg(c->device);
-  KVSEP_HIP(dg.err);
-  // as launch_batch: under capture the capture's own set, no cross-stream events and no allocation
-  // (kvsep_crc32c_reserve sizes the SST arrays too)
-  bool capturing = false;
-  Scratch* psc = nullptr;
-  int rc = stream_scratch(c, s, c->sc, &capturing, &psc);
-  if (rc) return rc;
-  Scratch& sc = *psc;
-  rc = capturing ? KVSEP_OK : acquire(sc, s);
-  if (rc) return rc;
-  rc = ensure_sst(sc, count, capturing);
-  if (rc) return rc;
-  if (list && list->bad_cap) {
-    rc = ensure_list(sc, count, capturing);
-    if (rc) return rc;
-  }
-  if (count) {
-    sst_verify_prep_kernel<<<unsigned((count + 255) / 256), 256, 0, s>>>(static_cast<const uint8_t*>(file_base), off,
-                                                                        len, sc.d_sst_len1, sc.d_sst_stored, count);
-    KVSEP_HIP(hipGetLastError());
-  }
-  rc = launch_batch_in(c, sc, s, capturing, file_base, off, sc.d_sst_len1, nullptr, sc.d_sst_stored, out, first_bad,
-                       nbad, count, total_bytes + count, max_len ? max_len + 1 : 0);
-  if (!rc && list)
-    rc = launch_list(sc, s, capturing, out, sc.d_sst_stored, verdict_nbad(sc, first_bad, nbad), *list, count);
-  if (rc) {
-    if (!capturing) (void)release(sc, s);
-    return rc;
-  }
-  return capturing ? KVSEP_OK : release(sc, s);
+  return with_scratch(
+      c, s, c->sc,
+      [&](Scratch& sc, bool capturing) {  // (kvsep_crc32c_reserve sizes the SST arrays too)
+        int rc = ensure_sst(sc, count, capturing);
+        if (!rc && list && list->bad_cap) rc = ensure_list(sc, count, capturing);
+        return rc;
+      },
+      [&](Scratch& sc, bool capturing) {
+        if (count) {
+          sst_verify_prep_kernel<<<unsigned((count + 255) / 256), 256, 0, s>>>(
+              static_cast<const uint8_t*>(file_base), off, len, sc.sst.p, sc.sst.q, count);
+          KVSEP_HIP(hipGetLastError());
+        }
+        int rc = launch_batch_in(c, sc, s, capturing, file_base, off, sc.sst.p, nullptr, sc.sst.q, out, first_bad, nbad,
+                                 count, total_bytes + count, max_len ? max_len + 1 : 0);
+        if (!rc && list)
+          rc = launch_list(sc, s, capturing, out, sc.sst.q, verdict_nbad(sc, first_bad, nbad), *list, count);
+        return rc;
+      });
 }
 
 int sst_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, const uint64_t* off,
@@ -1355,14 +1312,6 @@ struct OffsetsCall {
   uint64_t count, nseg;
 };
 
-// The scratch the calls on `s` run on (the capture's own set under capture), checked to hold an offsets pass of `count`
-// blocks: refuses a captured call that was not reserved for before anything is enqueued, and allocates for an eager one.
-int offsets_scratch(kvsep_crc32c_ctx* c, hipStream_t s, uint64_t count, bool* capturing, Scratch** psc) {
-  int rc = stream_scratch(c, s, c->sc, capturing, psc);
-  if (rc) return rc;
-  return ensure_offsets(**psc, count, *capturing);
-}
-
 // The three kernels on `s`, on a scratch the caller has acquired and sized (ensure_offsets).  An empty batch runs the
 // write kernel alone, which then touches no scratch.
 int launch_offsets_in(Scratch& sc, hipStream_t s, const OffsetsCall& o) {
@@ -1376,11 +1325,12 @@ int launch_offsets_in(Scratch& sc, hipStream_t s, const OffsetsCall& o) {
   a.count = o.count, a.nseg = o.nseg;
   a.dst_off = o.dst_off, a.end = o.end, a.nkept = o.nkept;
   if (nt) {
-    a.ext = sc.d_off_ext;
-    a.tile_sum = sc.d_off_tile;
-    a.tile_kept = sc.d_off_tile + nt;
-    a.tile_base = sc.d_off_tile + 2 * nt;
-    a.grand = sc.d_off_tile + 3 * nt;
+    const offsets::TileWords w = offsets::tile_words(nt);
+    a.ext = sc.off.p;
+    a.tile_sum = sc.off.q + w.sum;
+    a.tile_kept = sc.off.q + w.kept;
+    a.tile_base = sc.off.q + w.base;
+    a.grand = sc.off.q + w.grand;
     offsets_tile_sum_kernel<<<unsigned(nt), offsets::kThreads, 0, s>>>(a);
     KVSEP_HIP(hipGetLastError());
     offsets_tile_scan_kernel<<<1, offsets::kScanThreads, 0, s>>>(a.tile_sum, a.tile_kept, a.tile_base, a.grand, nt);
@@ -1391,26 +1341,19 @@ int launch_offsets_in(Scratch& sc, hipStream_t s, const OffsetsCall& o) {
   return KVSEP_OK;
 }
 
-// The offsets pass as a call of its own: its scratch is bracketed here.  `then`, when given, is enqueued inside the
-// bracket (a copy that reads the pass's scratch).  The caller holds the context's mutex.
+// What an offsets pass over `count` blocks needs.
+auto offsets_needs(uint64_t count) {
+  return [=](Scratch& sc, bool capturing) { return ensure_offsets(sc, count, capturing); };
+}
+
+// The offsets pass as a call of its own, in its own scratch bracket.  `then`, when given, is enqueued inside the bracket
+// (a copy that reads the pass's scratch).  The caller holds the context's mutex.
 template <typename Then>
 int launch_offsets(kvsep_crc32c_ctx* c, hipStream_t s, const OffsetsCall& o, Then then) {
-  DeviceGuard dg(c->device);
-  KVSEP_HIP(dg.err);
-  bool capturing = false;
-  Scratch* psc = nullptr;
-  int rc = offsets_scratch(c, s, o.count, &capturing, &psc);
-  if (rc) return rc;
-  Scratch& sc = *psc;
-  rc = capturing ? KVSEP_OK : acquire(sc, s);
-  if (rc) return rc;
-  rc = launch_offsets_in(sc, s, o);
-  if (!rc) rc = then(sc);
-  if (rc) {
-    if (!capturing) (void)release(sc, s);
-    return rc;
-  }
-  return capturing ? KVSEP_OK : release(sc, s);
+  return with_scratch(c, s, c->sc, offsets_needs(o.count), [&](Scratch& sc, bool) {
+    const int rc = launch_offsets_in(sc, s, o);
+    return rc ? rc : then(sc);
+  });
 }
 
 int launch_offsets(kvsep_crc32c_ctx* c, hipStream_t s, const OffsetsCall& o) {
@@ -1477,14 +1420,9 @@ int kvsep_sst_salvage_device(kvsep_crc32c_ctx* c, void* stream, const void* file
   if (!c) return set_err(KVSEP_EINVAL, "kvsep_sst_salvage_device: null ctx");
   std::lock_guard<std::mutex> g(c->mu);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  {  // refused before anything is enqueued (the read check makes its own checks first thing, too)
-    DeviceGuard dg(c->device);
-    KVSEP_HIP(dg.err);
-    bool capturing = false;
-    Scratch* psc = nullptr;
-    rc = offsets_scratch(c, s, count, &capturing, &psc);
-    if (rc) return rc;
-  }
+  // refused before anything is enqueued (the read check makes its own checks first thing, too)
+  rc = check_scratch(c, s, offsets_needs(count));
+  if (rc) return rc;
   const ListOut l{nullptr, 0, ok};
   rc = sst_verify_locked(c, stream, file_base, off, len, out, first_bad, nbad, count, total_bytes, max_len, &l);
   if (rc) return rc;
@@ -1496,7 +1434,7 @@ int kvsep_sst_salvage_device(kvsep_crc32c_ctx* c, void* stream, const void* file
                           return launch_pack<PackPlain>(
                               c, s,
                               PackArgs{static_cast<const uint8_t*>(file_base), off,
-                                       reinterpret_cast<const uint64_t*>(sc.d_off_ext), nullptr,
+                                       reinterpret_cast<const uint64_t*>(sc.off.p), nullptr,
                                        static_cast<uint8_t*>(dst), dst_bytes, dst_off, count, count, nullptr, nullptr, 0,
                                        0});
                         });
@@ -1514,14 +1452,9 @@ int kvsep_vlog_frame_auto_device(kvsep_crc32c_ctx* c, void* stream, const void* 
     return set_err(KVSEP_EINVAL, "kvsep_vlog_frame_auto_device: null seg_crc or crc_out");
   std::lock_guard<std::mutex> g(c->mu);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  {  // refused before anything is enqueued
-    DeviceGuard dg(c->device);
-    KVSEP_HIP(dg.err);
-    bool capturing = false;
-    Scratch* psc = nullptr;
-    rc = offsets_scratch(c, s, count, &capturing, &psc);
-    if (rc) return rc;
-  }
+  // refused before anything is enqueued
+  rc = check_scratch(c, s, offsets_needs(count));
+  if (rc) return rc;
   rc = launch_gather(c, s, base, seg_off, seg_len, first, nullptr, seg_crc, crc_out, count, nseg, total_bytes, max_len);
   if (rc) return rc;
   // a payload the header's LE32 length cannot hold is refused as kvsep_vlog_frame_offsets refuses it: no offset for it
@@ -1586,16 +1519,6 @@ int log_accept_args(const char* who, const kvsep_crc32c_ctx* c, const LogAcceptC
   return KVSEP_OK;
 }
 
-// The scratch of a log call on `s`, checked to hold `nblocks` blocks (and the offsets pass over them when `walk`):
-// refuses a captured call that was not reserved for before anything is enqueued, and allocates for an eager one.
-int log_scratch(kvsep_crc32c_ctx* c, hipStream_t s, uint64_t nblocks, bool walk, bool* capturing, Scratch** psc) {
-  int rc = stream_scratch(c, s, c->sc, capturing, psc);
-  if (rc) return rc;
-  rc = ensure_log(**psc, nblocks, *capturing);
-  if (!rc && walk) rc = ensure_offsets(**psc, nblocks, *capturing);
-  return rc;
-}
-
 // The walk on a scratch the caller has acquired and sized: count, the offsets pass over the counts, fill.
 int launch_log_walk_in(Scratch& sc, hipStream_t s, const LogWalkCall& w) {
   const uint64_t nb = logrun::block_count(w.n);
@@ -1605,8 +1528,9 @@ int launch_log_walk_in(Scratch& sc, hipStream_t s, const LogWalkCall& w) {
   a.off = w.off, a.len = w.len, a.stored = w.stored, a.type = w.type;
   a.cap = w.cap;
   a.nrec = reinterpret_cast<const unsigned long long*>(w.nrec);
-  a.cnt = sc.d_log + 1;
-  a.base = sc.d_log + 1 + nb;
+  const logrun::Words lw = logrun::words(nb);
+  a.cnt = sc.log.p + lw.cnt;
+  a.base = sc.log.p + lw.base;
   if (nb) {
     log_count_kernel<<<unsigned(logrun::grid_for(nb)), logrun::kThreads, 0, s>>>(a.img, a.n, nb, a.cnt);
     KVSEP_HIP(hipGetLastError());
@@ -1631,12 +1555,13 @@ int launch_log_accept_in(Scratch& sc, hipStream_t s, const LogAcceptCall& w) {
   a.nrec = reinterpret_cast<const unsigned long long*>(w.nrec);
   a.cap = w.cap;
   a.accept = w.accept, a.gap = w.gap, a.dropped = w.dropped, a.bad_length = w.bad_length;
-  a.stop = sc.d_log;
-  a.first = sc.d_log + 1 + 2 * nb;
-  a.state = sc.d_log + 1 + 3 * nb;
-  a.cand = sc.d_log + 1 + 4 * nb;
-  a.drop = sc.d_log + 1 + 5 * nb;
-  a.badlen = sc.d_log + 1 + 6 * nb;
+  const logrun::Words lw = logrun::words(nb);
+  a.stop = sc.log.p + lw.stop;
+  a.first = sc.log.p + lw.first;
+  a.state = sc.log.p + lw.state;
+  a.cand = sc.log.p + lw.cand;
+  a.drop = sc.log.p + lw.drop;
+  a.badlen = sc.log.p + lw.badlen;
   if (nb) {
     log_block_kernel<<<unsigned(logrun::grid_for(nb)), logrun::kThreads, 0, s>>>(a);
     KVSEP_HIP(hipGetLastError());
@@ -1652,31 +1577,39 @@ int launch_log_accept_in(Scratch& sc, hipStream_t s, const LogAcceptCall& w) {
   return KVSEP_OK;
 }
 
-// A log call as a call of its own: its scratch is bracketed here.  The caller holds the context's mutex.
+// What a log call over an image of n bytes needs: the log words, the offsets pass over the blocks when it walks, and
+// when it checks verify_count checksums their CRC words and plan -- refused with the rest, not between two enqueued
+// steps.
+auto log_needs(kvsep_crc32c_ctx* c, uint64_t n, bool walk, uint64_t verify_count) {
+  return [=](Scratch& sc, bool capturing) {
+    const uint64_t nb = logrun::block_count(n);
+    int rc = ensure_log(sc, nb, capturing);
+    if (!rc && walk) rc = ensure_offsets(sc, nb, capturing);
+    if (!rc && verify_count) rc = ensure_sst(sc, verify_count, capturing);
+    if (!rc && verify_count)
+      rc = ensure_plan_for(c, sc, verify_count, n, logrun::kBlock - logrun::kTypeAt, capturing);
+    return rc;
+  };
+}
+
+// A log call as a call of its own, in its own scratch bracket.  The caller holds the context's mutex.
 template <typename Body>
 int launch_log(kvsep_crc32c_ctx* c, hipStream_t s, uint64_t n, bool walk, uint64_t verify_count, Body body) {
-  DeviceGuard dg(c->device);
-  KVSEP_HIP(dg.err);
-  bool capturing = false;
-  Scratch* psc = nullptr;
-  int rc = log_scratch(c, s, logrun::block_count(n), walk, &capturing, &psc);
-  if (rc) return rc;
-  Scratch& sc = *psc;
-  if (verify_count) {  // the checksum step's CRC words, refused here rather than between two enqueued steps
-    rc = ensure_sst(sc, verify_count, capturing);
-    if (rc) return rc;
-    const Route r = route_batch(c, verify_count, n, logrun::kBlock - logrun::kTypeAt);
-    if (r.planned) rc = ensure_plan(sc, verify_count, plan::pieces_needed(r.piece_bytes, verify_count, n), capturing);
-    if (rc) return rc;
-  }
-  rc = capturing ? KVSEP_OK : acquire(sc, s);
-  if (rc) return rc;
-  rc = body(sc, capturing);
-  if (rc) {
-    if (!capturing) (void)release(sc, s);
-    return rc;
-  }
-  return capturing ? KVSEP_OK : release(sc, s);
+  return with_scratch(c, s, c->sc, log_needs(c, n, walk, verify_count), body);
+}
+
+// The walk, the checksum step and the accept pass of the read and records forms, on a scratch sized by log_needs.
+int launch_log_read_in(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capturing, const LogWalkCall& w,
+                       const LogAcceptCall& acc, uint8_t* ok) {
+  int r = launch_log_walk_in(sc, s, w);
+  // the checksum step of kvsep_log_verify_device over all cap elements: the padding has length 0, Value("") = 0 and
+  // Mask(0) != 0 = stored, so ok[] is 0 there
+  if (!r && w.cap)
+    r = launch_batch_in(c, sc, s, capturing, w.base, w.off, w.len, nullptr, nullptr, sc.sst.q, nullptr, nullptr, w.cap,
+                        w.n, logrun::kBlock - logrun::kTypeAt);
+  if (!r) r = launch_list(sc, s, capturing, sc.sst.q, w.stored, nullptr, ListOut{nullptr, 0, ok}, w.cap);
+  if (!r) r = launch_log_accept_in(sc, s, acc);
+  return r;
 }
 }  // namespace
 
@@ -1716,15 +1649,7 @@ int kvsep_log_read_device(kvsep_crc32c_ctx* c, void* stream, const void* base, u
   hipStream_t s = static_cast<hipStream_t>(stream);
   const LogWalkCall w{base, n, off, len, stored, type, cap, nrec};
   return launch_log(c, s, n, true, cap, [&](Scratch& sc, bool capturing) {
-    int r = launch_log_walk_in(sc, s, w);
-    // the checksum step of kvsep_log_verify_device over all cap elements: the padding has length 0, Value("") = 0 and
-    // Mask(0) != 0 = stored, so ok[] is 0 there
-    if (!r && cap)
-      r = launch_batch_in(c, sc, s, capturing, base, off, len, nullptr, nullptr, sc.d_sst_stored, nullptr, nullptr, cap,
-                          n, logrun::kBlock - logrun::kTypeAt);
-    if (!r) r = launch_list(sc, s, capturing, sc.d_sst_stored, stored, nullptr, ListOut{nullptr, 0, ok}, cap);
-    if (!r) r = launch_log_accept_in(sc, s, acc);
-    return r;
+    return launch_log_read_in(c, sc, s, capturing, w, acc, ok);
   });
 }
 
@@ -1754,20 +1679,16 @@ struct SstWalkCall {
   uint32_t* status;
 };
 
-// The scratch of an SST walk on `s`, checked to hold a walk with `cap` slots (and the offsets pass over its runs):
-// refuses a captured call that was not reserved for before anything is enqueued, and allocates for an eager one.
-int sst_scratch(kvsep_crc32c_ctx* c, hipStream_t s, uint64_t n, uint64_t cap, bool* capturing, Scratch** psc) {
-  int rc = stream_scratch(c, s, c->sc, capturing, psc);
-  if (rc) return rc;
-  Scratch& sc = **psc;
-  rc = ensure_sstidx(sc, sst::runs_for(sc.cap_sstidx, cap), *capturing);
-  if (!rc) rc = ensure_offsets(sc, sst::runs_used(sc.cap_sstidx, n), *capturing);
+// What an SST walk with `cap` slots over an image of n bytes needs: the index words, and the offsets pass over its runs.
+int sst_walk_needs(Scratch& sc, bool capturing, uint64_t n, uint64_t cap) {
+  int rc = ensure_sstidx(sc, sst::runs_for(sc.sstidx.cap, cap), capturing);
+  if (!rc) rc = ensure_offsets(sc, sst::runs_used(sc.sstidx.cap, n), capturing);
   return rc;
 }
 
 // The walk on a scratch the caller has acquired and sized: count, stop, the offsets pass over the counts, fill.
 int launch_sst_walk_in(Scratch& sc, hipStream_t s, const SstWalkCall& w) {
-  const uint64_t runs = sst::runs_used(sc.cap_sstidx, w.n);  // sst_scratch made cap_sstidx >= 1
+  const uint64_t runs = sst::runs_used(sc.sstidx.cap, w.n);  // sst_walk_needs made the capacity >= 1
   SstIndexArgs a{};
   a.img = static_cast<const uint8_t*>(w.base);
   a.n = w.n;
@@ -1775,12 +1696,12 @@ int launch_sst_walk_in(Scratch& sc, hipStream_t s, const SstWalkCall& w) {
   a.runs = runs;
   a.handles = w.handles;
   a.crc = w.crc;
-  a.stored = sc.d_sst_stored;
+  a.stored = sc.sst.q;
   a.off = w.off, a.len = w.len, a.cap = w.cap;
   a.nblocks = reinterpret_cast<unsigned long long*>(w.nblocks);
   a.status = w.status;
-  a.stop = sc.d_sstidx;
-  a.cnt = sc.d_sstidx + sst::kStopWords;
+  a.stop = sc.sstidx.p;
+  a.cnt = sc.sstidx.p + sst::kStopWords;
   a.errbase = a.cnt + runs;
   a.wgstop = a.errbase + runs;
   const uint64_t nwg = sst::grid_for(runs);
@@ -1823,21 +1744,10 @@ int kvsep_sst_index_device(kvsep_crc32c_ctx* c, void* stream, const void* file_b
   if (!c) return set_err(KVSEP_EINVAL, "kvsep_sst_index_device: null ctx");
   std::lock_guard<std::mutex> g(c->mu);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  DeviceGuard dg(c->device);
-  KVSEP_HIP(dg.err);
-  bool capturing = false;
-  Scratch* psc = nullptr;
-  rc = sst_scratch(c, s, n, cap, &capturing, &psc);
-  if (rc) return rc;
-  Scratch& sc = *psc;
-  rc = capturing ? KVSEP_OK : acquire(sc, s);
-  if (rc) return rc;
-  rc = launch_sst_walk_in(sc, s, SstWalkCall{file_base, n, handle, nullptr, nullptr, off, len, cap, nblocks, status});
-  if (rc) {
-    if (!capturing) (void)release(sc, s);
-    return rc;
-  }
-  return capturing ? KVSEP_OK : release(sc, s);
+  const SstWalkCall w{file_base, n, handle, nullptr, nullptr, off, len, cap, nblocks, status};
+  return with_scratch(
+      c, s, c->sc, [&](Scratch& sc, bool capturing) { return sst_walk_needs(sc, capturing, n, cap); },
+      [&](Scratch& sc, bool) { return launch_sst_walk_in(sc, s, w); });
 }
 
 int kvsep_sst_table_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, uint64_t n, uint64_t* off,
@@ -1853,35 +1763,27 @@ int kvsep_sst_table_verify_device(kvsep_crc32c_ctx* c, void* stream, const void*
   if (!c) return set_err(KVSEP_EINVAL, "kvsep_sst_table_verify_device: null ctx");
   std::lock_guard<std::mutex> g(c->mu);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  DeviceGuard dg(c->device);
-  KVSEP_HIP(dg.err);
-  bool capturing = false;
-  Scratch* psc = nullptr;
-  rc = sst_scratch(c, s, n, cap, &capturing, &psc);
-  if (rc) return rc;
-  Scratch& sc = *psc;
-  // everything the two read checks and the list pass need, refused here rather than between two enqueued steps
   const uint64_t hint1 = max_len_hint ? max_len_hint + 1 : 0;
-  rc = ensure_sst(sc, cap, capturing);
-  if (!rc && bad_cap) rc = ensure_list(sc, cap, capturing);
-  if (rc) return rc;
-  if (capturing && (!sc.d_verify || !sc.d_counter || sc.cap_vslot < vslots_needed(c)))
-    return set_err(KVSEP_EINVAL, "verify under capture needs kvsep_crc32c_reserve first");
-  const Route r_index = route_batch(c, 1, n, 0), r_all = route_batch(c, cap, n + cap, hint1);
-  if (r_index.planned) rc = ensure_plan(sc, 1, plan::pieces_needed(r_index.piece_bytes, 1, n), capturing);
-  if (!rc && r_all.planned) rc = ensure_plan(sc, cap, plan::pieces_needed(r_all.piece_bytes, cap, n + cap), capturing);
-  if (rc) return rc;
-  rc = capturing ? KVSEP_OK : acquire(sc, s);
-  if (rc) return rc;
+  // the walk, and everything the two read checks and the list pass need, refused rather than between two enqueued steps
+  const auto needs = [&](Scratch& sc, bool capturing) {
+    int rc = sst_walk_needs(sc, capturing, n, cap);
+    if (!rc) rc = ensure_sst(sc, cap, capturing);
+    if (!rc && bad_cap) rc = ensure_list(sc, cap, capturing);
+    if (!rc && capturing && (!sc.verify.p || !sc.counter.p || sc.vslot.cap < vslots_needed(c)))
+      rc = set_err(KVSEP_EINVAL, "verify under capture needs kvsep_crc32c_reserve first");
+    if (!rc) rc = ensure_plan_for(c, sc, 1, n, 0, capturing);
+    if (!rc) rc = ensure_plan_for(c, sc, cap, n + cap, hint1, capturing);
+    return rc;
+  };
   const auto* img = static_cast<const uint8_t*>(file_base);
-  rc = [&]() -> int {
+  return with_scratch(c, s, c->sc, needs, [&](Scratch& sc, bool capturing) -> int {
     sst_footer_kernel<<<1, sst::kFooterThreads, 0, s>>>(img, n, handles, status);
     KVSEP_HIP(hipGetLastError());
     // the read check of the index block alone: its checksum into crc[0], its stored word into the scratch
     sst_table_prep_kernel<<<1, sst::kThreads, 0, s>>>(
-        SstPrepArgs{img, n, handles + 2, handles + 3, 1, nullptr, status, cap, sc.d_sst_len1, sc.d_sst_stored});
+        SstPrepArgs{img, n, handles + 2, handles + 3, 1, nullptr, status, cap, sc.sst.p, sc.sst.q});
     KVSEP_HIP(hipGetLastError());
-    int r = launch_batch_in(c, sc, s, capturing, file_base, handles + 2, sc.d_sst_len1, nullptr, nullptr, crc, nullptr,
+    int r = launch_batch_in(c, sc, s, capturing, file_base, handles + 2, sc.sst.p, nullptr, nullptr, crc, nullptr,
                             nullptr, 1, n, 0);
     if (r) return r;
     r = launch_sst_walk_in(sc, s, SstWalkCall{file_base, n, handles + 2, handles, crc, off, len, cap, nblocks, status});
@@ -1889,19 +1791,14 @@ int kvsep_sst_table_verify_device(kvsep_crc32c_ctx* c, void* stream, const void*
     // the read check and the list pass over all cap slots: padding has length 0 and passes
     sst_table_prep_kernel<<<unsigned(sst::grid_for(cap)), sst::kThreads, 0, s>>>(
         SstPrepArgs{img, n, off, len, cap, reinterpret_cast<const unsigned long long*>(nblocks), status, cap,
-                    sc.d_sst_len1, sc.d_sst_stored});
+                    sc.sst.p, sc.sst.q});
     KVSEP_HIP(hipGetLastError());
-    r = launch_batch_in(c, sc, s, capturing, file_base, off, sc.d_sst_len1, nullptr, sc.d_sst_stored, crc, first_bad,
+    r = launch_batch_in(c, sc, s, capturing, file_base, off, sc.sst.p, nullptr, sc.sst.q, crc, first_bad,
                         nbad, cap, n + cap, hint1);
     if (r) return r;
-    return launch_list(sc, s, capturing, crc, sc.d_sst_stored, verdict_nbad(sc, first_bad, nbad),
+    return launch_list(sc, s, capturing, crc, sc.sst.q, verdict_nbad(sc, first_bad, nbad),
                        ListOut{bad_idx, bad_cap, ok}, cap);
-  }();
-  if (rc) {
-    if (!capturing) (void)release(sc, s);
-    return rc;
-  }
-  return capturing ? KVSEP_OK : release(sc, s);
+  });
 }
 
 }  // extern "C"
@@ -1950,9 +1847,10 @@ int launch_chains_in(Scratch& sc, hipStream_t s, const ChainCall& k) {
   a.first = k.first, a.whole = k.whole, a.frag_off = k.frag_off, a.frag_len = k.frag_len;
   a.nchain = k.nchain, a.nwhole = k.nwhole;
   if (nt) {
-    a.sum = sc.d_chain;
-    a.in = sc.d_chain + nt;
-    a.grand = sc.d_chain + 2 * nt;
+    const chain::TileWords w = chain::tile_words(nt);
+    a.sum = sc.chain.p + w.sum;
+    a.in = sc.chain.p + w.in;
+    a.grand = sc.chain.p + w.grand;
     chain_tile_kernel<<<unsigned(nt), chain::kThreads, 0, s>>>(a);
     KVSEP_HIP(hipGetLastError());
     chain_scan_kernel<<<1, chain::kScanThreads, 0, s>>>(a.sum, a.in, a.grand, nt);
@@ -1975,22 +1873,9 @@ int kvsep_log_chains_device(kvsep_crc32c_ctx* c, void* stream, const uint8_t* ty
   if (rc) return rc;
   std::lock_guard<std::mutex> g(c->mu);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  DeviceGuard dg(c->device);
-  KVSEP_HIP(dg.err);
-  bool capturing = false;
-  Scratch* psc = nullptr;
-  rc = stream_scratch(c, s, c->sc, &capturing, &psc);
-  if (!rc) rc = ensure_chain(*psc, cap, capturing);
-  if (rc) return rc;
-  Scratch& sc = *psc;
-  rc = capturing ? KVSEP_OK : acquire(sc, s);
-  if (rc) return rc;
-  rc = launch_chains_in(sc, s, k);
-  if (rc) {
-    if (!capturing) (void)release(sc, s);
-    return rc;
-  }
-  return capturing ? KVSEP_OK : release(sc, s);
+  return with_scratch(
+      c, s, c->sc, [&](Scratch& sc, bool capturing) { return ensure_chain(sc, cap, capturing); },
+      [&](Scratch& sc, bool) { return launch_chains_in(sc, s, k); });
 }
 
 int kvsep_log_records_device(kvsep_crc32c_ctx* c, void* stream, const void* base, uint64_t n, uint64_t* off,
@@ -2012,23 +1897,15 @@ int kvsep_log_records_device(kvsep_crc32c_ctx* c, void* stream, const void* base
   if (rc) return rc;
   std::lock_guard<std::mutex> g(c->mu);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  {  // the chains pass and the layout over cap chains: refused before anything is enqueued
-    DeviceGuard dg(c->device);
-    KVSEP_HIP(dg.err);
-    bool capturing = false;
-    Scratch* psc = nullptr;
-    rc = offsets_scratch(c, s, cap, &capturing, &psc);
-    if (!rc) rc = ensure_chain(*psc, cap, capturing);
-    if (rc) return rc;
-  }
   const LogWalkCall w{base, n, off, len, stored, type, cap, nrec};
-  return launch_log(c, s, n, true, cap, [&](Scratch& sc, bool capturing) {
-    int r = launch_log_walk_in(sc, s, w);
-    if (!r && cap)
-      r = launch_batch_in(c, sc, s, capturing, base, off, len, nullptr, nullptr, sc.d_sst_stored, nullptr, nullptr, cap,
-                          n, logrun::kBlock - logrun::kTypeAt);
-    if (!r) r = launch_list(sc, s, capturing, sc.d_sst_stored, stored, nullptr, ListOut{nullptr, 0, ok}, cap);
-    if (!r) r = launch_log_accept_in(sc, s, acc);
+  const auto needs = [&](Scratch& sc, bool capturing) {  // the layout and the chains pass over cap chains, then the read
+    int rc = ensure_offsets(sc, cap, capturing);
+    if (!rc) rc = ensure_chain(sc, cap, capturing);
+    if (!rc) rc = log_needs(c, n, true, cap)(sc, capturing);
+    return rc;
+  };
+  return with_scratch(c, s, c->sc, needs, [&](Scratch& sc, bool capturing) {
+    int r = launch_log_read_in(c, sc, s, capturing, w, acc, ok);
     if (!r) r = launch_chains_in(sc, s, k);
     // The layout: chain j is the fragments [first[j], first[j + 1]), kept when whole.  The walk's offsets pass is done
     // with the pass's scratch by now: its result went to the log words, which the fill kernel has read.
@@ -2037,7 +1914,7 @@ int kvsep_log_records_device(kvsep_crc32c_ctx* c, void* stream, const void* base
                                                nwhole, cap, cap});
     if (!r && rec_len && cap) {
       chain_reclen_kernel<<<unsigned(chain::reclen_grid(cap)), chain::kThreads, 0, s>>>(
-          sc.d_off_ext, rec_len, cap);
+          sc.off.p, rec_len, cap);
       if (hipGetLastError() != hipSuccess) r = set_err(KVSEP_EHIP, "chain_reclen_kernel launch");
     }
     if (!r)
@@ -2076,23 +1953,13 @@ int kvsep_log_frame_device(kvsep_crc32c_ctx* c, void* stream, const void* base, 
   } seeds;
   std::lock_guard<std::mutex> g(c->mu);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  DeviceGuard dg(c->device);
-  KVSEP_HIP(dg.err);
   // every scratch size is checked before the first kernel: the two words of this pass, and the plan of the checksum
   // call when the context's piece size puts 32,761-byte fragments through one
-  bool capturing = false;
-  Scratch* psc = nullptr;
-  int rc = stream_scratch(c, s, c->sc, &capturing, &psc);
-  if (!rc) rc = ensure_logw(*psc, logw::fill_lanes(count, frag_cap), capturing);
-  if (rc) return rc;
-  Scratch& sc = *psc;
-  if (frag_cap) {
-    const Route r = route_batch(c, frag_cap, total_bytes, logw::kAvail);
-    if (r.planned) rc = ensure_plan(sc, frag_cap, plan::pieces_needed(r.piece_bytes, frag_cap, total_bytes), capturing);
-    if (rc) return rc;
-  }
-  rc = capturing ? KVSEP_OK : acquire(sc, s);
-  if (rc) return rc;
+  const auto needs = [&](Scratch& sc, bool capturing) {
+    int rc = ensure_logw(sc, logw::fill_lanes(count, frag_cap), capturing);
+    if (!rc && frag_cap) rc = ensure_plan_for(c, sc, frag_cap, total_bytes, logw::kAvail, capturing);
+    return rc;
+  };
   LogwArgs a{};
   a.off = off, a.len = len, a.keep = keep, a.count = count;
   a.b0 = logw::start_state(dest_length);
@@ -2100,9 +1967,9 @@ int kvsep_log_frame_device(kvsep_crc32c_ctx* c, void* stream, const void* base, 
   a.rec_at = rec_at, a.frag_first = frag_first;
   a.frag_off = frag_off, a.frag_len = frag_len, a.frag_at = frag_at, a.frag_type = frag_type, a.frag_cap = frag_cap;
   a.nfrag = nfrag, a.written = written;
-  a.rec = sc.d_logw_rec, a.seed = sc.d_logw_seed;
   a.s1 = seeds.v[logw::kFull], a.s2 = seeds.v[logw::kFirst], a.s3 = seeds.v[logw::kMiddle], a.s4 = seeds.v[logw::kLast];
-  const auto body = [&]() -> int {
+  return with_scratch(c, s, c->sc, needs, [&](Scratch& sc, bool capturing) -> int {
+    a.rec = sc.logw.p, a.seed = sc.logw.q;
     logw_layout_kernel<<<1, logw::kLayoutThreads, 0, s>>>(a);
     KVSEP_HIP(hipGetLastError());
     const uint64_t lanes = logw::fill_lanes(count, frag_cap);
@@ -2113,7 +1980,7 @@ int kvsep_log_frame_device(kvsep_crc32c_ctx* c, void* stream, const void* base, 
     if (!frag_cap) return KVSEP_OK;
     // the fragments' checksums: the batched form over all frag_cap slots, the seeds as init (a padding slot has length
     // 0 and seed 0: frag_crc = 0 there), then the copy that stamps each header in front of its fragment
-    int r = launch_batch_in(c, sc, s, capturing, base, frag_off, frag_len, sc.d_logw_seed, nullptr, frag_crc, nullptr,
+    int r = launch_batch_in(c, sc, s, capturing, base, frag_off, frag_len, sc.logw.q, nullptr, frag_crc, nullptr,
                             nullptr, frag_cap, total_bytes, logw::kAvail);
     if (r) return r;
     // fragment f is segment f: no first[]; a padding slot's kSkip lies in no destination (pack::fits)
@@ -2121,13 +1988,7 @@ int kvsep_log_frame_device(kvsep_crc32c_ctx* c, void* stream, const void* base, 
                                 PackArgs{static_cast<const uint8_t*>(base), frag_off, frag_len, nullptr,
                                          static_cast<uint8_t*>(dst), dst_bytes, frag_at, frag_cap, frag_cap, frag_crc,
                                          frag_type, 0, 0});
-  };
-  rc = body();
-  if (rc) {
-    if (!capturing) (void)release(sc, s);
-    return rc;
-  }
-  return capturing ? KVSEP_OK : release(sc, s);
+  });
 }
 
 int kvsep_sst_verify_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, const uint64_t* off,

@@ -13,44 +13,55 @@ struct kvsep_crc32c_ctx;
 
 namespace kvsep {
 
-// Device scratch of one in-flight batch: the piece plan (planned mode), the work counter, the verify
-// defaults and the SST-verify arrays.  A scratch object is reused call after call; `last_use` orders a
-// call on a different stream behind the previous user, so reuse across streams is race-free.  The host
-// pipeline gives each staging slot its own Scratch so the two slots' batches overlap, and every graph capture takes a
-// capture set's Scratch of its own (crc32c_device.hip, capture_scratch).
+struct Scratch;
+
+// One device array of a Scratch, or two that are sized together, with the capacity they hold -- in the unit the form
+// that uses them counts in (blocks, tiles, records, lanes, restart runs), never bytes.  Nothing but these functions
+// (crc32c_device.hip) allocates or frees a scratch array or sets a capacity; every array is a hipMalloc of its own.
+// kEvenEmpty: the array exists even for a need of 0 (kernels that run on empty inputs write its stop word or totals).
+constexpr bool kEvenEmpty = true;
+template <typename T, bool kAlways = false, typename U = char>
+struct __attribute__((visibility("hidden"))) DevBuf {  // (no symbol of it leaves the library)
+  T* p = nullptr;
+  U* q = nullptr;  // the second array of a pair (null where there is none)
+  uint64_t cap = 0;
+  bool holds(uint64_t need) const { return need <= cap && (p || !kAlways); }
+  void drop();  // frees; cap = 0
+  // np elements of p and nq of q, then cap = need; a failure leaves the buffer dropped
+  int alloc(uint64_t need, uint64_t np, uint64_t nq = 0);
+  // Room for `need`: nothing to do when it holds; under capture a refusal (KVSEP_EINVAL, `what`); else waits for the
+  // scratch's last user (quiesce), drops and allocates -- a pair is freed whole before either array is allocated again.
+  int ensure(Scratch& sc, uint64_t need, bool capturing, const char* what, uint64_t np, uint64_t nq = 0);
+};
+
+// Device scratch of one in-flight batch: the piece plan (planned mode), the work counter, the verify words and the
+// arrays of the SST, list, offsets, log, chains, log-frame and SST-index forms.  A scratch object is reused call after
+// call; `last_use` orders a call on a different stream behind the previous user, so reuse across streams is race-free
+// (crc32c_device.hip, with_scratch).  The host pipeline gives each staging slot its own Scratch so the two slots'
+// batches overlap, and every graph capture takes a capture set's Scratch of its own (stream_scratch).
 struct Scratch {
-  uint64_t cap_count = 0, cap_pieces = 0;
-  uint64_t* d_counts = nullptr;
-  uint64_t* d_pstart = nullptr;
-  uint32_t* d_pblk = nullptr;
-  uint32_t* d_partial = nullptr;
-  void* d_scan_tmp = nullptr;
-  size_t scan_tmp_bytes = 0;
-  uint32_t* d_counter = nullptr;
-  unsigned long long* d_verify = nullptr;  // [first_bad, nbad] when the caller passes none, then the accumulator set
-  bool vacc_dirty = false;                  // a failed eager call may have posted to the set: reset before its next use
-  unsigned long long* d_vslot = nullptr;    // captured verify calls: one verdict slot (2 words) per publishing workgroup
-  uint32_t cap_vslot = 0;
-  uint64_t* d_sst_len1 = nullptr;           // SST verify: len + 1 ...
-  uint32_t* d_sst_stored = nullptr;         // ... and the stored trailer words
-  uint64_t cap_sst = 0;
-  uint32_t* d_tile_cnt = nullptr;            // list forms: bad blocks per tile of the batch ...
-  unsigned long long* d_tile_base = nullptr;  // ... and their exclusive prefix sum (crc32c_verdicts.inc)
-  uint64_t cap_tiles = 0;
-  unsigned long long* d_off_ext = nullptr;   // offsets pass: the extent of every block ...
-  unsigned long long* d_off_tile = nullptr;  // ... and per tile [sum | kept | base], then the two grand totals
-  uint64_t cap_off = 0;                      // blocks both are sized for (crc32c_offsets.inc)
-  unsigned long long* d_log = nullptr;       // log reader: per 32 KiB block [cnt | base | first | state | cand | drop |
-  uint64_t cap_log = 0;                      // badlen], then the stop word (crc32c_logwalk.inc); blocks it is sized for
-  unsigned long long* d_chain = nullptr;     // chains pass: per tile of records [summary | incoming state and base], then
-  uint64_t cap_chain = 0;                    // the two grand totals (crc32c_logchain.inc); records it is sized for
-  uint32_t* d_logw_rec = nullptr;            // log write side: a word per record ...
-  uint32_t* d_logw_seed = nullptr;           // ... and per fragment slot (crc32c_logframe.inc)
-  uint64_t cap_logw = 0;                     // records / fragment slots both are sized for
-  // SST index walk (crc32c_sstindex.inc): [keep_before, stop], then per restart run [cnt | error, later base], then a
-  // word per workgroup of the count kernel (its lowest run with an error): sst::scratch_words(cap_sstidx) words
-  unsigned long long* d_sstidx = nullptr;
-  uint64_t cap_sstidx = 0;  // restart runs d_sstidx is sized for
+  DevBuf<uint64_t, false, uint64_t> plan_blocks;  // the plan: counts | pstart (one more), per block
+  DevBuf<uint32_t, false, uint32_t> plan_pieces;  // ... and pblk | partial, per piece
+  DevBuf<unsigned char> scan_tmp;                 // ... and hipcub's scan storage, in bytes
+  DevBuf<uint32_t> counter;                       // the guided schedule's work counter
+  DevBuf<unsigned long long> verify;  // [first_bad, nbad] when the caller passes none, then the accumulator set
+  bool vacc_dirty = false;            // a failed eager call may have posted to the set: reset before its next use
+  DevBuf<unsigned long long> vslot;   // captured verify calls: a verdict slot (2 words) per publishing workgroup
+  DevBuf<uint64_t, false, uint32_t> sst;  // SST verify: len + 1 | the stored trailer words, per block
+  // list forms: bad blocks per tile of the batch | their exclusive prefix sum (crc32c_verdicts.inc), per tile
+  DevBuf<uint32_t, false, unsigned long long> tiles;
+  // offsets pass (crc32c_offsets.inc): the extent of every block | offsets::scratch_words tile words, per block
+  DevBuf<unsigned long long, false, unsigned long long> off;
+  DevBuf<unsigned long long, kEvenEmpty> log;    // log reader (crc32c_logwalk.inc): logrun::scratch_words, per block
+  DevBuf<unsigned long long, kEvenEmpty> chain;  // chains pass (crc32c_logchain.inc): chain::scratch_words, per record
+  // log write side (crc32c_logframe.inc): a word per record | per fragment slot, per record / fragment slot
+  DevBuf<uint32_t, kEvenEmpty, uint32_t> logw;
+  DevBuf<unsigned long long, kEvenEmpty> sstidx;  // SST index walk (crc32c_sstindex.inc): sst::scratch_words, per run
+  template <typename F>
+  void each_buf(F f) {  // every array above: what free_scratch frees
+    f(plan_blocks), f(plan_pieces), f(scan_tmp), f(counter), f(verify), f(vslot), f(sst), f(tiles), f(off), f(log),
+        f(chain), f(logw), f(sstidx);
+  }
   hipEvent_t last_use = nullptr;
   hipStream_t last_stream = nullptr;
   bool used = false;

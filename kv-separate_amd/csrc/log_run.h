@@ -48,6 +48,20 @@ KVSEP_HD uint64_t pad_grid(uint64_t nblocks, uint64_t cap) {
   return grid_for(items ? items : 1);
 }
 
+// The reader's scratch words, one array: the stop index, then kLogWords per block -- its record count, the records
+// before it, its first record, `pending` state, stop candidate, dropped bytes and bad-length bytes.  A call over nblocks
+// blocks slices it at words(nblocks); an array that holds nblocks blocks has scratch_words(nblocks) words.
+constexpr uint64_t kStopWords = 1;
+constexpr uint64_t kLogWords = 7;
+struct Words {
+  uint64_t stop, cnt, base, first, state, cand, drop, badlen;
+};
+KVSEP_HD Words words(uint64_t nblocks) {
+  const uint64_t w = kStopWords, nb = nblocks;
+  return {0, w, w + nb, w + 2 * nb, w + 3 * nb, w + 4 * nb, w + 5 * nb, w + 6 * nb};
+}
+KVSEP_HD uint64_t scratch_words(uint64_t nblocks) { return kStopWords + kLogWords * nblocks; }
+
 // ---- headers
 enum Head : uint32_t { kRecord = 0, kBadLength = 1, kZero = 2, kTrailer = 3 };
 

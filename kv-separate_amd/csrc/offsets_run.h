@@ -47,6 +47,15 @@ KVSEP_HD uint64_t add_sat(uint64_t a, uint64_t b) { return a + b < a ? kSaturate
 
 KVSEP_HD uint64_t tile_count(uint64_t count) { return (count + kTile - 1) / kTile; }
 
+// The pass's tile words, one array: per tile a sum, a kept count and a base, then the two grand totals.  A call over
+// ntiles tiles slices it at tile_words(ntiles); an array that holds `count` blocks has scratch_words(count) words.
+constexpr uint64_t kGrandWords = 2;
+struct TileWords {
+  uint64_t sum, kept, base, grand;
+};
+KVSEP_HD TileWords tile_words(uint64_t ntiles) { return {0, ntiles, 2 * ntiles, 3 * ntiles}; }
+KVSEP_HD uint64_t scratch_words(uint64_t count) { return tile_words(tile_count(count)).grand + kGrandWords; }
+
 // The block of lane `lane` in row `row` of wave `wave` of tile `tile`: consecutive lanes own consecutive blocks.
 KVSEP_HD uint64_t block_index(uint64_t tile, uint32_t wave, uint32_t row, uint32_t lane) {
   return tile * kTile + (uint64_t(wave) * kRows + row) * kWaveLanes + lane;

@@ -9,9 +9,11 @@
 //   launch_geometry logw     COUNT FRAG_CAP
 //   launch_geometry concat   COUNT
 //   launch_geometry pack     COUNT TARGET_WORKGROUPS   (also prints "short_wgs N" and "team N" for PackArgs)
+//   launch_geometry scratch  offsets COUNT | log NBLOCKS | chains CAP
 //
 // One line per kernel, in stream order: "<kernel> <grid> <threads>"; a grid of 0 is a kernel the call does not launch.
-// `constants` prints "<name> <value>" lines instead.
+// `constants` prints "<name> <value>" lines instead, and so does `scratch`: "words" an array sized for the argument
+// holds, then the word offset of each slice a call over it takes -- what the launch code sizes and slices with.
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -53,6 +55,19 @@ int main(int argc, char** argv) {
                 pack::kChunkBlocks);
     std::printf("logw_kAhead %u\nlogw_kWaveLanes %u\nlogw_kBlock %u\nlogw_kAvail %u\nlogw_kFillThreads %u\n", logw::kAhead,
                 logw::kWaveLanes, logw::kBlock, logw::kAvail, logw::kFillThreads);
+  } else if (!std::strcmp(what, "scratch") && argc > 2 && !std::strcmp(argv[2], "offsets")) {
+    const offsets::TileWords w = offsets::tile_words(offsets::tile_count(arg(3)));
+    std::printf("words %" PRIu64 "\ntile_sum %" PRIu64 "\ntile_kept %" PRIu64 "\ntile_base %" PRIu64 "\ngrand %" PRIu64
+                "\n", offsets::scratch_words(arg(3)), w.sum, w.kept, w.base, w.grand);
+  } else if (!std::strcmp(what, "scratch") && argc > 2 && !std::strcmp(argv[2], "log")) {
+    const logrun::Words w = logrun::words(arg(3));
+    std::printf("words %" PRIu64 "\nstop %" PRIu64 "\ncnt %" PRIu64 "\nbase %" PRIu64 "\nfirst %" PRIu64 "\nstate %" PRIu64
+                "\ncand %" PRIu64 "\ndrop %" PRIu64 "\nbadlen %" PRIu64 "\n", logrun::scratch_words(arg(3)), w.stop, w.cnt,
+                w.base, w.first, w.state, w.cand, w.drop, w.badlen);
+  } else if (!std::strcmp(what, "scratch") && argc > 2 && !std::strcmp(argv[2], "chains")) {
+    const chain::TileWords w = chain::tile_words(chain::tile_count(arg(3)));
+    std::printf("words %" PRIu64 "\nsum %" PRIu64 "\nin %" PRIu64 "\ngrand %" PRIu64 "\n", chain::scratch_words(arg(3)),
+                w.sum, w.in, w.grand);
   } else if (!std::strcmp(what, "offsets")) {
     offsets_pass(arg(2));
   } else if (!std::strcmp(what, "verdicts")) {

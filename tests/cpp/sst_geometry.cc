@@ -40,9 +40,13 @@ int main(int argc, char** argv) {
     std::printf("kThreads %u\nkStopWords %" PRIu64 "\nkMaskOfZero %u\nkNoMatch %u\nkFooter %" PRIu64 "\n", sst::kThreads,
                 sst::kStopWords, sst::kMaskOfZero, sst::kNoMatch, sst::kFooter);
     std::printf("offsets_kTile %u\n", offsets::kTile);
-  } else if (!std::strcmp(what, "scratch")) {  // RUNS: words of the walk's scratch, workgroups of its count kernel
+  } else if (!std::strcmp(what, "scratch")) {  // RUNS: words of the walk's scratch, workgroups of its count kernel,
+    // then the offsets pass over the runs: its tiles, its tile words and the word offset of each slice of them
+    const offsets::TileWords w = offsets::tile_words(offsets::tile_count(arg(2)));
     std::printf("words %" PRIu64 "\nworkgroups %" PRIu64 "\ntiles %" PRIu64 "\n", sst::scratch_words(arg(2)),
                 sst::grid_for(arg(2)), offsets::tile_count(arg(2)));
+    std::printf("tile_words %" PRIu64 "\ntile_sum %" PRIu64 "\ntile_kept %" PRIu64 "\ntile_base %" PRIu64 "\ngrand %" PRIu64
+                "\n", offsets::scratch_words(arg(2)), w.sum, w.kept, w.base, w.grand);
   } else if (!std::strcmp(what, "walk")) {
     walk(arg(2), arg(3));
   } else if (!std::strcmp(what, "table")) {

@@ -106,6 +106,16 @@ class Env:
     def const_threads(self, family):
         return int(self._ask(family, 1, 4)[0].split()[2])
 
+    def scratch(self, family, n):
+        """{"words": the words an array sized for n holds, slice: its word offset} from the pure header of `family`."""
+        return {k: int(v) for k, v in (ln.split() for ln in self._ask("scratch", family, n))}
+
+    def tile_words(self, c, count):
+        """The offsets pass's tile array for `count` blocks and its slices, as OffsetsArgs fields."""
+        w = self.scratch("offsets", count)
+        tile = c.scratch("tile", 8 * w.pop("words"))
+        return {k: tile + 8 * at for k, at in w.items()}
+
     def geometry(self, *args):
         """[(kernel, grid, threads)] of a call, in stream order, from tests/cpp/launch_geometry.cc."""
         return [(k, int(g), int(t)) for k, g, t in (ln.split() for ln in self._ask(*args))]
@@ -258,8 +268,7 @@ def run_offsets(env, tag, seg_len, first, keep, before, head, tail, start, max_s
         v["nkept"] = c.output("nkept", 8)
     if nt:  # the launch code's carve-up of the pass's two allocations
         v["ext"] = c.scratch("ext", 8 * count)
-        tile = c.scratch("tile", 8 * (3 * nt + 2))
-        v.update(tile_sum=tile, tile_kept=tile + 8 * nt, tile_base=tile + 16 * nt, grand=tile + 24 * nt)
+        v.update(env.tile_words(c, count))
     args = c.sargs("offsets_tile_sum", "OffsetsArgs", v)
     for kernel, grid, threads in geo:
         if not grid:
@@ -426,8 +435,9 @@ def test_chains(env, count, form):
         v.update(off=c.input("off", off), len=c.input("len", ln), frag_off=c.output("frag_off", 8 * cap),
                  frag_len=c.output("frag_len", 8 * cap), nwhole=c.output("nwhole", 8))
     if nt:
-        sc = c.scratch("chain", 8 * (2 * nt + 2))
-        v.update(sum=sc, **{"in": sc + 8 * nt}, grand=sc + 16 * nt)
+        w = env.scratch("chains", cap)
+        sc = c.scratch("chain", 8 * w.pop("words"))
+        v.update({k: sc + 8 * at for k, at in w.items()})
     args = c.sargs("chain_tile", "ChainArgs", v)
     c.launch("chain_tile", geo[0][1], geo[0][2], args)
     if nt:
@@ -646,19 +656,19 @@ def run_log(env, tag, img, cap_delta, skew):
     geo = dict((k, (g, t)) for k, g, t in env.geometry("log", n, cap))
     nb = -(-n // env.const["log_kBlock"])  # the image's 32 KiB blocks
     d_img = c.image(img, skew)
-    words = 7 * nb + 1
+    lw = env.scratch("log", nb)
+    words = lw.pop("words")
     d_log = c.scratch("log", 8 * words)
     nt = geo["offsets_tile_sum_kernel"][0]
     d_nrec = c.output("nrec", 8)
     wv = dict(img=d_img, n=n, nblocks=nb, off=c.output("off", 8 * cap), len=c.output("len", 8 * cap),
-              stored=c.output("stored", 4 * cap), type=c.output("type", cap), cap=cap, nrec=d_nrec, cnt=d_log + 8,
-              base=d_log + 8 + 8 * nb)
+              stored=c.output("stored", 4 * cap), type=c.output("type", cap), cap=cap, nrec=d_nrec,
+              cnt=d_log + 8 * lw["cnt"], base=d_log + 8 * lw["base"])
     c.launch("log_count", *geo["log_count_kernel"], c.pargs("log_count", [d_img, n, nb, wv["cnt"]]))
     ov = dict(seg_len=wv["cnt"], max_size=M64, count=nb, nseg=nb, dst_off=wv["base"], end=d_nrec)
     if nt:
         ov["ext"] = c.scratch("ext", 8 * nb)
-        tile = c.scratch("tile", 8 * (3 * nt + 2))
-        ov.update(tile_sum=tile, tile_kept=tile + 8 * nt, tile_base=tile + 16 * nt, grand=tile + 24 * nt)
+        ov.update(env.tile_words(c, nb))
     oargs = c.sargs("offsets_tile_sum", "OffsetsArgs", ov)
     c.launch("offsets_tile_sum", *geo["offsets_tile_sum_kernel"], oargs)
     if nt:
@@ -686,9 +696,8 @@ def run_log(env, tag, img, cap_delta, skew):
     av = dict(img=d_img, n=n, nblocks=nb, off=a.input("off", off[:held]), len=a.input("len", ln[:held]),
               type=a.input("type", ty[:held]), ok=a.input("ok", ok), nrec=a.input("nrec", np.array([nrec], np.uint64)),
               cap=cap, accept=a.output("accept", cap), gap=a.output("gap", cap), dropped=a.output("dropped", 8),
-              bad_length=a.output("bad_length", 8), stop=d_log, first=d_log + 8 * (1 + 2 * nb),
-              state=d_log + 8 * (1 + 3 * nb), cand=d_log + 8 * (1 + 4 * nb), drop=d_log + 8 * (1 + 5 * nb),
-              badlen=d_log + 8 * (1 + 6 * nb))
+              bad_length=a.output("bad_length", 8),
+              **{k: d_log + 8 * lw[k] for k in ("stop", "first", "state", "cand", "drop", "badlen")})
     aargs = a.sargs("log_block", "LogAcceptArgs", av)
     a.launch("log_block", *geo["log_block_kernel"], aargs)
     a.launch("log_stop", *geo["log_stop_kernel"], a.pargs("log_stop", [av["cand"], nb, av["stop"]]))

@@ -111,7 +111,7 @@ def run(env, geo, tag, img, cap, runs, skew, table, index=None, crc_ok=True):
     nt, nwg = sizes["tiles"], sizes["workgroups"]
     d_idx = c.scratch("sstidx", 8 * sizes["words"])
     d_ext = c.scratch("ext", 8 * runs)
-    d_tile = c.scratch("tile", 8 * (3 * nt + 2))
+    d_tile = c.scratch("tile", 8 * sizes["tile_words"])
     d_off, d_len = c.output("off", 8 * cap), c.output("len", 8 * cap)
     d_nb, d_st = c.output("nblocks", 8), c.output("status", 4)
     stop, cnt = d_idx, d_idx + 8 * geo.const["kStopWords"]
@@ -138,7 +138,7 @@ def run(env, geo, tag, img, cap, runs, skew, table, index=None, crc_ok=True):
     wv = dict(img=d_img, n=n, handle=d_handle, runs=runs, handles=d_handles, crc=d_crc, stored=d_stored, off=d_off,
               len=d_len, cap=cap, nblocks=d_nb, status=d_st, stop=stop, cnt=cnt, errbase=errbase, wgstop=wgstop)
     ov = dict(seg_len=cnt, keep_before=stop, max_size=M64, count=runs, nseg=runs, dst_off=errbase, end=d_nb, ext=d_ext,
-              tile_sum=d_tile, tile_kept=d_tile + 8 * nt, tile_base=d_tile + 16 * nt, grand=d_tile + 24 * nt)
+              **{k: d_tile + 8 * sizes[k] for k in ("tile_sum", "tile_kept", "tile_base", "grand")})
     preps = 0
     for kernel, grid, threads in kernels:
         if kernel == "sst_footer":
