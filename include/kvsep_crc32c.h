@@ -45,7 +45,9 @@ extern "C" {
  * kvsep_log_accept_gaps_device, kvsep_log_read_device) and its record assembly (kvsep_log_chains,
  * kvsep_log_chains_device, kvsep_log_records_device) and the device log / MANIFEST writer (kvsep_log_frame_layout,
  * kvsep_log_frame_device) and the SST table reader (kvsep_sst_footer, kvsep_sst_index_walk, kvsep_sst_index_device,
- * kvsep_sst_table_verify_device, the KVSEP_SST_* status codes).
+ * kvsep_sst_table_verify_device, the KVSEP_SST_* status codes) and the SST table writer (kvsep_sst_index_keys,
+ * kvsep_sst_index_keys_device, kvsep_sst_index_build, kvsep_sst_footer_build, kvsep_sst_index_build_device,
+ * kvsep_sst_table_finish_device, kvsep_sst_table_rewrite_device, KVSEP_SST_SHARED_KEY, the KVSEP_SSTW_* status codes).
  * The reference's C++ symbol leveldb::crc32c::Extend is not in this library: it is in the libkvsep_leveldb_abi.so
  * shim. */
 #define KVSEP_ABI_VERSION 4
@@ -652,6 +654,97 @@ int kvsep_sst_table_verify_device(kvsep_crc32c_ctx* ctx, void* stream, const voi
                                   uint64_t* len, uint32_t* crc, uint64_t* first_bad, uint64_t* nbad, uint64_t* bad_idx,
                                   uint64_t bad_cap, uint8_t* ok, uint64_t cap, uint64_t max_len_hint,
                                   uint64_t* nblocks, uint64_t* handles, uint32_t* status);
+
+/* ---------------------------------------------------------------- SST table writer: index block build, table rewrite
+ * The write side of the reader above: kvsep_sst_salvage_device leaves the blocks that passed back to back with their
+ * trailers, which is not a table -- it has no index block, no metaindex block and no footer.  These forms finish it on
+ * the same stream with no host step.  ABI 4 gained them as new entry points and defines only.
+ *
+ * Two facts make the rewrite correct without looking inside data blocks: an index entry's key is a separator (>= every
+ * key of its block, < the first key of the next), and dropping entry j leaves every remaining separator valid for the
+ * blocks that remain.  So the new index is the kept entries' key bytes, copied from the old index block, with the new
+ * handles.  The reference writes index blocks at block_restart_interval = 1 (table/table_builder.cc:36,92): every key
+ * is stored whole and contiguous.  Expanding prefix-compressed keys is not built: */
+#define KVSEP_SST_SHARED_KEY 8       /* keys walk: an entry shares key bytes with the one before it (shared != 0), so
+                                        its key has no contiguous place in the block */
+/* The walk, with keys: kvsep_sst_index_walk / kvsep_sst_index_device with two more outputs, under the same rules (first
+ * error wins; outputs written for exactly cap elements, zero from min(*nblocks, cap) on; *nblocks the full count).
+ * key_off[i] is the offset of entry i's key bytes (host form: in blk; device form: in the image) and key_len[i] their
+ * length.  An entry with shared != 0 stops the walk with KVSEP_SST_SHARED_KEY; the entries before it are emitted. */
+int kvsep_sst_index_keys(const char* blk, uint64_t blk_len, uint64_t* off, uint64_t* len, uint64_t* key_off,
+                         uint64_t* key_len, uint64_t cap, uint64_t* nblocks, uint32_t* status);
+int kvsep_sst_index_keys_device(kvsep_crc32c_ctx* ctx, void* stream, const void* file_base, uint64_t n,
+                                const uint64_t* handle, uint64_t* off, uint64_t* len, uint64_t* key_off,
+                                uint64_t* key_len, uint64_t cap, uint64_t* nblocks, uint32_t* status);
+/* The status word of the builder forms: */
+#define KVSEP_SSTW_OK 0
+#define KVSEP_SSTW_TOO_LARGE 1 /* the block would reach 2^32 bytes (restart offsets are 32-bit), or a key_len exceeds
+                                  2^32 - 1; sums saturate as in the offsets pass */
+#define KVSEP_SSTW_NO_ROOM 2   /* position + block + 5 (the table form: + 13 before and + 48 after) > dst_bytes */
+#define KVSEP_SSTW_SOURCE 3    /* rewrite only: the source's status is KVSEP_SST_BAD_FOOTER, _INDEX_CHECKSUM,
+                                  _INDEX_COMPRESSED or _SHARED_KEY: there is no index to rewrite */
+/* The index block BlockBuilder produces at restart interval 1 for the kept entries in order, with its trailer:
+ *   entry i is kept iff keep[i] != 0 (or keep is null) and blk_off[i] != KVSEP_OFFSET_SKIP -- the salvage's ok[] and
+ *   dst_off[] go in as they are; its key is key_base[key_off[i], + key_len[i]), its value the handle (blk_off[i],
+ *   blk_len[i]);
+ *   entries: varint32(0) varint32(key_len) varint32(value_len) key varint64(off) varint64(len); then restart[k] = byte
+ *   position of the k-th kept entry (LE32) and the restart count; with no kept entry the reference's empty block, one
+ *   restart of 0 and a count of 1 (8 bytes);
+ *   the trailer [0][Mask(Extend(Value(block), "\0", 1)) LE32] follows; *out_len is the block's length without it.
+ * The block goes to dst + at.  On a refusal nothing is written and *out_len holds the needed length (0 when too large).
+ * Host form: host arrays, `at` a value.  Returns KVSEP_EINVAL for a null required pointer. */
+int kvsep_sst_index_build(const char* key_base, const uint64_t* key_off, const uint64_t* key_len,
+                          const uint64_t* blk_off, const uint64_t* blk_len, const uint8_t* keep, uint64_t count,
+                          char* dst, uint64_t dst_bytes, uint64_t at, uint64_t* out_len, uint32_t* status);
+/* The 48-byte footer (Footer::EncodeTo, table/format.cc:23-35): the metaindex and index handles as varint64s, zero
+ * padding to 40 bytes, the magic. */
+int kvsep_sst_footer_build(uint64_t meta_off, uint64_t meta_len, uint64_t index_off, uint64_t index_len, char out[48]);
+/* The device forms.  Every pointer except ctx is DEVICE memory, `at` / `data_end` included (the position depends on a
+ * salvage's *end; the kernels read it); nothing is read back; asynchronous on `stream`; no atomics, results identical
+ * from run to run.  The argument refusals come before the context or any device is touched: a null required pointer,
+ * count > 2^32 - 1 -- each KVSEP_EINVAL.  The refusals above are decided on the device from the totals before anything
+ * is written.
+ * Kernels: a size kernel, the offsets pass twice (byte positions; ranks among the kept), the fill kernel (a wavefront
+ * stages its 64 entries in LDS and stores the range in aligned 16-B granules, byte stores at the edges; a range over
+ * 4 KiB is written entry by entry by the whole wave), the batched checksum over the one block, a tail kernel.
+ * Scratch: four words per entry plus the offsets pass's and a one-block plan: kvsep_crc32c_reserve(ctx, count,
+ * total_bytes >= min(dst_bytes, 2^32)) makes a call allocation-free and capturable; a captured call over its
+ * reservation fails with KVSEP_EINVAL before anything is enqueued.
+ * Memory touched: key_off / key_len / blk_off / blk_len / keep are read for count elements; key bytes are read only
+ * for kept entries, inside [key_off[i], key_off[i] + key_len[i]) -- when a wave's range is over 4 KiB, inside the
+ * naturally aligned 16-B granules of key_base that hold such a byte; dst is written only inside the block and its
+ * trailer, nothing is read-modify-written. */
+int kvsep_sst_index_build_device(kvsep_crc32c_ctx* ctx, void* stream, const void* key_base, const uint64_t* key_off,
+                                 const uint64_t* key_len, const uint64_t* blk_off, const uint64_t* blk_len,
+                                 const uint8_t* keep, uint64_t count, void* dst, uint64_t dst_bytes, const uint64_t* at,
+                                 uint64_t* out_len, uint32_t* status);
+/* Finishes a table whose data blocks end at *data_end: the empty metaindex block with its trailer (13 bytes) at
+ * *data_end, the index block above at *data_end + 13, the 48-byte footer after its trailer; *index_len as *out_len
+ * above, *table_bytes the table's size (0 after a refusal, which writes nothing).  dst is written only inside
+ * [*data_end, *table_bytes).  The output has no filter block: filter offsets are tied to the old layout, and
+ * Table::Open accepts a table without one. */
+int kvsep_sst_table_finish_device(kvsep_crc32c_ctx* ctx, void* stream, const void* key_base, const uint64_t* key_off,
+                                  const uint64_t* key_len, const uint64_t* blk_off, const uint64_t* blk_len,
+                                  const uint8_t* keep, uint64_t count, void* dst, uint64_t dst_bytes,
+                                  const uint64_t* data_end, uint64_t* index_len, uint64_t* table_bytes,
+                                  uint32_t* status);
+/* Source image in, finished table out, on one stream: kvsep_sst_table_verify_device with the keys walk (off / len /
+ * crc / ok / cap / max_len_hint / nblocks / handles / status as there; key_off / key_len have cap elements); a keep
+ * mask of ok[i] for the data slots i < min(*nblocks, cap - 2); the salvage's layout (dst_off[cap], *nkept, nullable)
+ * and copy; kvsep_sst_table_finish_device with blk_off = dst_off (index_len / table_bytes / wstatus as there).
+ * A source status of KVSEP_SST_BAD_FOOTER, _INDEX_CHECKSUM, _INDEX_COMPRESSED or _SHARED_KEY writes nothing:
+ * *table_bytes = 0, *wstatus = KVSEP_SSTW_SOURCE.  Any other entry error keeps the entries before it, as the salvage
+ * does.  KVSEP_SST_CAP (more data blocks than cap - 2 slots) does not refuse either: the output is a finished table of
+ * the first cap - 2 data blocks that passed, *wstatus is KVSEP_SSTW_OK, and *status / *nblocks are what tell the caller
+ * that blocks past the slots were left out -- size cap from the index length to rule it out.  With every block good and the source laid out as TableBuilder lays it out without a filter policy (data blocks
+ * back to back from 0, then the metaindex block), the output equals the source byte for byte.
+ * Reserve as for the table verify and the builder: kvsep_crc32c_reserve(ctx, count >= max(cap, index_len / 4),
+ * total_bytes >= max(n + cap, dst_bytes)). */
+int kvsep_sst_table_rewrite_device(kvsep_crc32c_ctx* ctx, void* stream, const void* file_base, uint64_t n, void* dst,
+                                   uint64_t dst_bytes, uint64_t* off, uint64_t* len, uint64_t* key_off,
+                                   uint64_t* key_len, uint32_t* crc, uint8_t* ok, uint64_t* dst_off, uint64_t cap,
+                                   uint64_t max_len_hint, uint64_t* nblocks, uint64_t* nkept, uint64_t* handles,
+                                   uint32_t* status, uint64_t* index_len, uint64_t* table_bytes, uint32_t* wstatus);
 
 /* ---------------------------------------------------------------- several GPUs in one process
  * Blocks are independent, so a batch is cut into contiguous block ranges balanced by bytes and each range runs on

@@ -54,6 +54,7 @@
 #include "chain_run.h"
 #include "logw_run.h"
 #include "sst_run.h"
+#include "sstw_run.h"
 
 namespace kvsep {
 
@@ -69,6 +70,7 @@ namespace kvsep {
 #include "crc32c_logchain.inc" // chain_*_kernel: the chains pass, FIRST / MIDDLE / LAST fragments into records
 #include "crc32c_logframe.inc" // logw_*_kernel: the log / MANIFEST write side, records into fragments and pads
 #include "crc32c_sstindex.inc" // sst_*_kernel: the SST footer, the index-block walk, the table form's slots
+#include "crc32c_sstbuild.inc" // sst_keys_*_kernel, sstw_*_kernel: the walk with keys, the index block builder, the footer
 
 }  // namespace kvsep
 
@@ -311,6 +313,12 @@ int ensure_sstidx(Scratch& sc, uint64_t runs, bool capturing = false) {
   return sc.sstidx.ensure(sc, runs, capturing,
                           "a captured SST index walk larger than kvsep_crc32c_reserve sized its capture set for",
                           sst::scratch_words(runs));
+}
+
+int ensure_sstw(Scratch& sc, uint64_t count, bool capturing = false) {
+  return sc.sstw.ensure(sc, count, capturing,
+                        "a captured SST index build larger than kvsep_crc32c_reserve sized its capture set for",
+                        sstw::scratch_words(count));
 }
 
 // What a list form adds to its verify call: bad_idx[0, min(nbad, bad_cap)) and / or ok[0, count).
@@ -952,6 +960,7 @@ int reserve_scratch(kvsep_crc32c_ctx* c, Scratch& sc, uint64_t count, uint64_t t
   if (!rc) rc = ensure_chain(sc, count);
   if (!rc) rc = ensure_logw(sc, count);
   if (!rc) rc = ensure_sstidx(sc, sst::runs_for(sst::runs_reserved(count), 0));
+  if (!rc) rc = ensure_sstw(sc, count);
   if (rc) return rc;
   return ensure_plan(sc, count, plan::pieces_reserved(c->piece_bytes, c->piece_auto, c->num_cus, count, total_bytes));
 }
@@ -1677,6 +1686,9 @@ struct SstWalkCall {
   uint64_t cap;
   uint64_t* nblocks;
   uint32_t* status;
+  bool keys = false;            // the keys walk: where each emitted entry's key lies in the image, and its length
+  uint64_t* key_off = nullptr;
+  uint64_t* key_len = nullptr;
 };
 
 // What an SST walk with `cap` slots over an image of n bytes needs: the index words, and the offsets pass over its runs.
@@ -1705,7 +1717,8 @@ int launch_sst_walk_in(Scratch& sc, hipStream_t s, const SstWalkCall& w) {
   a.errbase = a.cnt + runs;
   a.wgstop = a.errbase + runs;
   const uint64_t nwg = sst::grid_for(runs);
-  sst_index_count_kernel<<<unsigned(nwg), sst::kThreads, 0, s>>>(a);
+  if (w.keys) sst_keys_count_kernel<<<unsigned(nwg), sst::kThreads, 0, s>>>(a);
+  else sst_index_count_kernel<<<unsigned(nwg), sst::kThreads, 0, s>>>(a);
   KVSEP_HIP(hipGetLastError());
   sst_index_stop_kernel<<<1, sst::kThreads, 0, s>>>(a.wgstop, nwg, a.errbase, a.stop);
   KVSEP_HIP(hipGetLastError());
@@ -1715,7 +1728,11 @@ int launch_sst_walk_in(Scratch& sc, hipStream_t s, const SstWalkCall& w) {
                                          reinterpret_cast<const uint64_t*>(a.stop), 0, 0, 0, ~uint64_t(0),
                                          reinterpret_cast<uint64_t*>(a.errbase), w.nblocks, nullptr, runs, runs});
   if (rc) return rc;
-  sst_index_fill_kernel<<<unsigned(sst::pad_grid(runs, w.cap)), sst::kThreads, 0, s>>>(a);
+  if (w.keys)
+    sst_keys_fill_kernel<<<unsigned(sst::pad_grid(runs, w.cap)), sst::kThreads, 0, s>>>(
+        SstKeysArgs{a, w.key_off, w.key_len});
+  else
+    sst_index_fill_kernel<<<unsigned(sst::pad_grid(runs, w.cap)), sst::kThreads, 0, s>>>(a);
   KVSEP_HIP(hipGetLastError());
   return KVSEP_OK;
 }
@@ -1730,6 +1747,177 @@ int sst_walk_args(const char* who, const void* base, uint64_t n, const void* off
                                                  : nullptr;
   if (!what) return KVSEP_OK;
   return set_err(KVSEP_EINVAL, (std::string(who) + ": " + what).c_str());
+}
+// The whole-table verify (and, with key_off / key_len, its keys walk), as a step other forms share.
+struct SstTableCall {
+  const void* base;
+  uint64_t n;
+  uint64_t* off;
+  uint64_t* len;
+  uint64_t* key_off;  // null: the plain walk
+  uint64_t* key_len;
+  uint32_t* crc;
+  uint64_t* first_bad;
+  uint64_t* nbad;
+  uint64_t* bad_idx;
+  uint64_t bad_cap;
+  uint8_t* ok;
+  uint64_t cap, max_len_hint;
+  uint64_t* nblocks;
+  uint64_t* handles;
+  uint32_t* status;
+};
+
+int sst_table_args(const char* who, const SstTableCall& t) {
+  const std::string w(who);
+  if (t.cap < 2) return set_err(KVSEP_EINVAL, (w + ": cap below 2 (the metaindex and index slots)").c_str());
+  int rc = sst_walk_args(who, t.base, t.n, t.off, t.len, t.cap, t.nblocks, t.status);
+  if (rc) return rc;
+  if (!t.crc || !t.handles) return set_err(KVSEP_EINVAL, (w + ": null crc or handles").c_str());
+  if (!t.bad_idx && t.bad_cap) return set_err(KVSEP_EINVAL, (w + ": null bad_idx with bad_cap > 0").c_str());
+  return KVSEP_OK;
+}
+
+// The walk, and everything the two read checks and the list pass need, refused rather than between two enqueued steps.
+int sst_table_needs(kvsep_crc32c_ctx* c, Scratch& sc, bool capturing, const SstTableCall& t) {
+  const uint64_t hint1 = t.max_len_hint ? t.max_len_hint + 1 : 0;
+  int rc = sst_walk_needs(sc, capturing, t.n, t.cap);
+  if (!rc) rc = ensure_sst(sc, t.cap, capturing);
+  if (!rc && t.bad_cap) rc = ensure_list(sc, t.cap, capturing);
+  if (!rc && capturing && (!sc.verify.p || !sc.counter.p || sc.vslot.cap < vslots_needed(c)))
+    rc = set_err(KVSEP_EINVAL, "verify under capture needs kvsep_crc32c_reserve first");
+  if (!rc) rc = ensure_plan_for(c, sc, 1, t.n, 0, capturing);
+  if (!rc) rc = ensure_plan_for(c, sc, t.cap, t.n + t.cap, hint1, capturing);
+  return rc;
+}
+
+int launch_sst_table_in(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capturing, const SstTableCall& t) {
+  const auto* img = static_cast<const uint8_t*>(t.base);
+  const uint64_t hint1 = t.max_len_hint ? t.max_len_hint + 1 : 0;
+  sst_footer_kernel<<<1, sst::kFooterThreads, 0, s>>>(img, t.n, t.handles, t.status);
+  KVSEP_HIP(hipGetLastError());
+  // the read check of the index block alone: its checksum into crc[0], its stored word into the scratch
+  sst_table_prep_kernel<<<1, sst::kThreads, 0, s>>>(
+      SstPrepArgs{img, t.n, t.handles + 2, t.handles + 3, 1, nullptr, t.status, t.cap, sc.sst.p, sc.sst.q});
+  KVSEP_HIP(hipGetLastError());
+  int r = launch_batch_in(c, sc, s, capturing, t.base, t.handles + 2, sc.sst.p, nullptr, nullptr, t.crc, nullptr,
+                          nullptr, 1, t.n, 0);
+  if (r) return r;
+  SstWalkCall w{t.base, t.n, t.handles + 2, t.handles, t.crc, t.off, t.len, t.cap, t.nblocks, t.status};
+  w.keys = t.key_off != nullptr, w.key_off = t.key_off, w.key_len = t.key_len;
+  r = launch_sst_walk_in(sc, s, w);
+  if (r) return r;
+  // the read check and the list pass over all cap slots: padding has length 0 and passes
+  sst_table_prep_kernel<<<unsigned(sst::grid_for(t.cap)), sst::kThreads, 0, s>>>(
+      SstPrepArgs{img, t.n, t.off, t.len, t.cap, reinterpret_cast<const unsigned long long*>(t.nblocks), t.status,
+                  t.cap, sc.sst.p, sc.sst.q});
+  KVSEP_HIP(hipGetLastError());
+  r = launch_batch_in(c, sc, s, capturing, t.base, t.off, sc.sst.p, nullptr, sc.sst.q, t.crc, t.first_bad, t.nbad,
+                      t.cap, t.n + t.cap, hint1);
+  if (r) return r;
+  return launch_list(sc, s, capturing, t.crc, sc.sst.q, verdict_nbad(sc, t.first_bad, t.nbad),
+                     ListOut{t.bad_idx, t.bad_cap, t.ok}, t.cap);
+}
+
+// ---- the SST table writer on the device (crc32c_sstbuild.inc)
+
+static_assert(sstw::kOk == KVSEP_SSTW_OK && sstw::kTooLarge == KVSEP_SSTW_TOO_LARGE &&
+                  sstw::kNoRoom == KVSEP_SSTW_NO_ROOM && sstw::kSource == KVSEP_SSTW_SOURCE &&
+                  sst::kSharedKey == KVSEP_SST_SHARED_KEY,
+              "sstw_run.h and sst_run.h restate the public status codes");
+static_assert(sstw::kSkip == offsets::kSkip && sstw::kSkip == KVSEP_OFFSET_SKIP, "the builder reads the offsets pass's marks");
+
+struct SstBuildCall {
+  const void* key_base;
+  const uint64_t* key_off;
+  const uint64_t* key_len;
+  const uint64_t* blk_off;
+  const uint64_t* blk_len;
+  const uint8_t* keep;
+  uint64_t count;
+  void* dst;
+  uint64_t dst_bytes;
+  const uint64_t* at;
+  uint64_t* out_len;
+  uint32_t* status;
+  uint64_t* table_bytes;   // non-null: the table form (metaindex block before, footer after)
+  const uint32_t* source;  // the rewrite: the walk's status word
+};
+
+// The length hint of the builder's checksum: the block lies inside dst and stays below 2^32 bytes.
+uint64_t sst_build_hint(uint64_t dst_bytes) { return std::min<uint64_t>(dst_bytes, sstw::kMaxBlock); }
+
+int sst_build_needs(kvsep_crc32c_ctx* c, Scratch& sc, bool capturing, uint64_t count, uint64_t dst_bytes) {
+  int rc = ensure_sstw(sc, count, capturing);
+  if (!rc) rc = ensure_offsets(sc, count, capturing);
+  if (!rc && capturing && !sc.counter.p) rc = set_err(KVSEP_EINVAL, "graph capture needs kvsep_crc32c_reserve first");
+  if (!rc) rc = ensure_plan_for(c, sc, 1, sst_build_hint(dst_bytes), 0, capturing);
+  return rc;
+}
+
+int sst_build_args(const char* who, const SstBuildCall& b) {
+  const char* what = b.count && (!b.key_off || !b.key_len || !b.blk_off || !b.blk_len)
+                         ? "null key or handle array with count != 0"
+                     : !b.dst || !b.at || !b.out_len || !b.status ? "null dst, position, out_len or status"
+                     : b.count > 0xffffffffull                    ? "more than 2^32 - 1 entries"
+                                                                  : nullptr;
+  if (!what) return KVSEP_OK;
+  return set_err(KVSEP_EINVAL, (std::string(who) + ": " + what).c_str());
+}
+
+// Mask(Extend(Value(the empty block), "\0", 1)): the table form's metaindex trailer word, computed once.
+uint32_t sst_meta_masked() {
+  static const uint32_t word = [] {
+    char blk[sstw::kEmptyBlock + 1];
+    for (uint32_t j = 0; j <= sstw::kEmptyBlock; ++j) blk[j] = char(sstw::meta_byte(j, 0));
+    return kvsep_crc32c_mask(kvsep_crc32c_extend_host(0, blk, sizeof blk));
+  }();
+  return word;
+}
+
+// The builder on a scratch the caller has acquired and sized (sst_build_needs): the size kernel, the offsets pass twice
+// (3 launches each), the fill kernel, the batched checksum over the one block, the tail kernel.
+int launch_sst_build_in(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capturing, const SstBuildCall& b) {
+  const sstw::Slices sl = sstw::slices(b.count);
+  SstBuildArgs a{};
+  a.key_base = static_cast<const uint8_t*>(b.key_base);
+  a.key_off = b.key_off, a.key_len = b.key_len, a.blk_off = b.blk_off, a.blk_len = b.blk_len, a.keep = b.keep;
+  a.count = b.count;
+  a.dst = static_cast<uint8_t*>(b.dst);
+  a.dst_bytes = b.dst_bytes;
+  a.at = reinterpret_cast<const unsigned long long*>(b.at);
+  a.lead = b.table_bytes ? sstw::kMetaFramed : 0;
+  a.trail = b.table_bytes ? sstw::kFooter : 0;
+  a.source = b.source;
+  a.size = sc.sstw.p + sl.size, a.flag = sc.sstw.p + sl.flag, a.pos = sc.sstw.p + sl.pos, a.rank = sc.sstw.p + sl.rank;
+  a.words = sc.sstw.p + sl.words;
+  a.out_len = b.out_len, a.status = b.status, a.table_bytes = b.table_bytes;
+  a.meta_masked = sst_meta_masked();
+  a.tabs = c->d_tabs;
+  auto* words = reinterpret_cast<uint64_t*>(a.words);
+  if (b.count) {
+    sstw_size_kernel<<<unsigned(sstw::grid_for(b.count)), sstw::kThreads, 0, s>>>(a);
+    KVSEP_HIP(hipGetLastError());
+  }
+  int rc = launch_offsets_in(sc, s,
+                             OffsetsCall{reinterpret_cast<const uint64_t*>(a.size), nullptr, nullptr, nullptr, 0, 0, 0,
+                                         ~uint64_t(0), reinterpret_cast<uint64_t*>(a.pos),
+                                         words + sstw::kEntriesBytes, nullptr, b.count, b.count});
+  if (!rc)
+    rc = launch_offsets_in(sc, s,
+                           OffsetsCall{reinterpret_cast<const uint64_t*>(a.flag), nullptr, nullptr, nullptr, 0, 0, 0,
+                                       ~uint64_t(0), reinterpret_cast<uint64_t*>(a.rank), words + sstw::kNKept, nullptr,
+                                       b.count, b.count});
+  if (rc) return rc;
+  sstw_fill_kernel<<<unsigned(sstw::grid_for(b.count)), sstw::kThreads, 0, s>>>(a);
+  KVSEP_HIP(hipGetLastError());
+  rc = launch_batch_in(c, sc, s, capturing, b.dst, words + sstw::kCrcOff, words + sstw::kCrcLen, nullptr, nullptr,
+                       reinterpret_cast<uint32_t*>(words + sstw::kCrc), nullptr, nullptr, 1,
+                       sst_build_hint(b.dst_bytes), 0);
+  if (rc) return rc;
+  sstw_tail_kernel<<<1, sstw::kTailThreads, 0, s>>>(a);
+  KVSEP_HIP(hipGetLastError());
+  return KVSEP_OK;
 }
 }  // namespace
 
@@ -1754,50 +1942,115 @@ int kvsep_sst_table_verify_device(kvsep_crc32c_ctx* c, void* stream, const void*
                                   uint64_t* len, uint32_t* crc, uint64_t* first_bad, uint64_t* nbad, uint64_t* bad_idx,
                                   uint64_t bad_cap, uint8_t* ok, uint64_t cap, uint64_t max_len_hint, uint64_t* nblocks,
                                   uint64_t* handles, uint32_t* status) {
-  const char* who = "kvsep_sst_table_verify_device";
-  if (cap < 2) return set_err(KVSEP_EINVAL, "kvsep_sst_table_verify_device: cap below 2 (the metaindex and index slots)");
-  int rc = sst_walk_args(who, file_base, n, off, len, cap, nblocks, status);
+  const SstTableCall t{file_base, n,       off, len,          nullptr, nullptr, crc,    first_bad,
+                       nbad,      bad_idx, bad_cap, ok, cap,     max_len_hint, nblocks, handles, status};
+  int rc = sst_table_args("kvsep_sst_table_verify_device", t);
   if (rc) return rc;
-  if (!crc || !handles) return set_err(KVSEP_EINVAL, "kvsep_sst_table_verify_device: null crc or handles");
-  if (!bad_idx && bad_cap) return set_err(KVSEP_EINVAL, "kvsep_sst_table_verify_device: null bad_idx with bad_cap > 0");
   if (!c) return set_err(KVSEP_EINVAL, "kvsep_sst_table_verify_device: null ctx");
   std::lock_guard<std::mutex> g(c->mu);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const uint64_t hint1 = max_len_hint ? max_len_hint + 1 : 0;
-  // the walk, and everything the two read checks and the list pass need, refused rather than between two enqueued steps
+  return with_scratch(
+      c, s, c->sc, [&](Scratch& sc, bool capturing) { return sst_table_needs(c, sc, capturing, t); },
+      [&](Scratch& sc, bool capturing) { return launch_sst_table_in(c, sc, s, capturing, t); });
+}
+
+int kvsep_sst_index_keys_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, uint64_t n,
+                                const uint64_t* handle, uint64_t* off, uint64_t* len, uint64_t* key_off,
+                                uint64_t* key_len, uint64_t cap, uint64_t* nblocks, uint32_t* status) {
+  const char* who = "kvsep_sst_index_keys_device";
+  int rc = sst_walk_args(who, file_base, n, off, len, cap, nblocks, status);
+  if (rc) return rc;
+  if (!handle) return set_err(KVSEP_EINVAL, "kvsep_sst_index_keys_device: null handle");
+  if (cap && (!key_off || !key_len))
+    return set_err(KVSEP_EINVAL, "kvsep_sst_index_keys_device: null key_off or key_len with cap != 0");
+  if (!c) return set_err(KVSEP_EINVAL, "kvsep_sst_index_keys_device: null ctx");
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  SstWalkCall w{file_base, n, handle, nullptr, nullptr, off, len, cap, nblocks, status};
+  w.keys = true, w.key_off = key_off, w.key_len = key_len;  // (null with cap == 0: nothing is stored)
+  return with_scratch(
+      c, s, c->sc, [&](Scratch& sc, bool capturing) { return sst_walk_needs(sc, capturing, n, cap); },
+      [&](Scratch& sc, bool) { return launch_sst_walk_in(sc, s, w); });
+}
+
+int kvsep_sst_index_build_device(kvsep_crc32c_ctx* c, void* stream, const void* key_base, const uint64_t* key_off,
+                                 const uint64_t* key_len, const uint64_t* blk_off, const uint64_t* blk_len,
+                                 const uint8_t* keep, uint64_t count, void* dst, uint64_t dst_bytes, const uint64_t* at,
+                                 uint64_t* out_len, uint32_t* status) {
+  const SstBuildCall b{key_base, key_off, key_len, blk_off, blk_len, keep,    count,
+                       dst,      dst_bytes, at,    out_len, status,  nullptr, nullptr};
+  int rc = sst_build_args("kvsep_sst_index_build_device", b);
+  if (rc) return rc;
+  if (!c) return set_err(KVSEP_EINVAL, "kvsep_sst_index_build_device: null ctx");
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return with_scratch(
+      c, s, c->sc, [&](Scratch& sc, bool capturing) { return sst_build_needs(c, sc, capturing, count, dst_bytes); },
+      [&](Scratch& sc, bool capturing) { return launch_sst_build_in(c, sc, s, capturing, b); });
+}
+
+int kvsep_sst_table_finish_device(kvsep_crc32c_ctx* c, void* stream, const void* key_base, const uint64_t* key_off,
+                                  const uint64_t* key_len, const uint64_t* blk_off, const uint64_t* blk_len,
+                                  const uint8_t* keep, uint64_t count, void* dst, uint64_t dst_bytes,
+                                  const uint64_t* data_end, uint64_t* index_len, uint64_t* table_bytes,
+                                  uint32_t* status) {
+  const SstBuildCall b{key_base, key_off,   key_len,  blk_off,   blk_len, keep,        count,
+                       dst,      dst_bytes, data_end, index_len, status,  table_bytes, nullptr};
+  int rc = sst_build_args("kvsep_sst_table_finish_device", b);
+  if (rc) return rc;
+  if (!table_bytes) return set_err(KVSEP_EINVAL, "kvsep_sst_table_finish_device: null table_bytes");
+  if (!c) return set_err(KVSEP_EINVAL, "kvsep_sst_table_finish_device: null ctx");
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return with_scratch(
+      c, s, c->sc, [&](Scratch& sc, bool capturing) { return sst_build_needs(c, sc, capturing, count, dst_bytes); },
+      [&](Scratch& sc, bool capturing) { return launch_sst_build_in(c, sc, s, capturing, b); });
+}
+
+int kvsep_sst_table_rewrite_device(kvsep_crc32c_ctx* c, void* stream, const void* file_base, uint64_t n, void* dst,
+                                   uint64_t dst_bytes, uint64_t* off, uint64_t* len, uint64_t* key_off,
+                                   uint64_t* key_len, uint32_t* crc, uint8_t* ok, uint64_t* dst_off, uint64_t cap,
+                                   uint64_t max_len_hint, uint64_t* nblocks, uint64_t* nkept, uint64_t* handles,
+                                   uint32_t* status, uint64_t* index_len, uint64_t* table_bytes, uint32_t* wstatus) {
+  const char* who = "kvsep_sst_table_rewrite_device";
+  const SstTableCall t{file_base, n,       off, len, key_off, key_len,      crc,     nullptr,
+                       nullptr,   nullptr, 0,   ok,  cap,     max_len_hint, nblocks, handles, status};
+  int rc = sst_table_args(who, t);
+  if (rc) return rc;
+  if (!key_off || !key_len || !ok || !dst_off || !dst || !index_len || !table_bytes || !wstatus)
+    return set_err(KVSEP_EINVAL, "kvsep_sst_table_rewrite_device: null argument");
+  if (!c) return set_err(KVSEP_EINVAL, "kvsep_sst_table_rewrite_device: null ctx");
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // every need of every step, before anything is enqueued
   const auto needs = [&](Scratch& sc, bool capturing) {
-    int rc = sst_walk_needs(sc, capturing, n, cap);
-    if (!rc) rc = ensure_sst(sc, cap, capturing);
-    if (!rc && bad_cap) rc = ensure_list(sc, cap, capturing);
-    if (!rc && capturing && (!sc.verify.p || !sc.counter.p || sc.vslot.cap < vslots_needed(c)))
-      rc = set_err(KVSEP_EINVAL, "verify under capture needs kvsep_crc32c_reserve first");
-    if (!rc) rc = ensure_plan_for(c, sc, 1, n, 0, capturing);
-    if (!rc) rc = ensure_plan_for(c, sc, cap, n + cap, hint1, capturing);
-    return rc;
+    int r = sst_table_needs(c, sc, capturing, t);
+    if (!r) r = sst_build_needs(c, sc, capturing, cap, dst_bytes);
+    return r;
   };
-  const auto* img = static_cast<const uint8_t*>(file_base);
   return with_scratch(c, s, c->sc, needs, [&](Scratch& sc, bool capturing) -> int {
-    sst_footer_kernel<<<1, sst::kFooterThreads, 0, s>>>(img, n, handles, status);
-    KVSEP_HIP(hipGetLastError());
-    // the read check of the index block alone: its checksum into crc[0], its stored word into the scratch
-    sst_table_prep_kernel<<<1, sst::kThreads, 0, s>>>(
-        SstPrepArgs{img, n, handles + 2, handles + 3, 1, nullptr, status, cap, sc.sst.p, sc.sst.q});
-    KVSEP_HIP(hipGetLastError());
-    int r = launch_batch_in(c, sc, s, capturing, file_base, handles + 2, sc.sst.p, nullptr, nullptr, crc, nullptr,
-                            nullptr, 1, n, 0);
+    int r = launch_sst_table_in(c, sc, s, capturing, t);
     if (r) return r;
-    r = launch_sst_walk_in(sc, s, SstWalkCall{file_base, n, handles + 2, handles, crc, off, len, cap, nblocks, status});
-    if (r) return r;
-    // the read check and the list pass over all cap slots: padding has length 0 and passes
-    sst_table_prep_kernel<<<unsigned(sst::grid_for(cap)), sst::kThreads, 0, s>>>(
-        SstPrepArgs{img, n, off, len, cap, reinterpret_cast<const unsigned long long*>(nblocks), status, cap,
-                    sc.sst.p, sc.sst.q});
+    const sstw::Slices sl = sstw::slices(cap);
+    auto* keep = reinterpret_cast<uint8_t*>(sc.sstw.p + sl.keep);
+    auto* words = reinterpret_cast<uint64_t*>(sc.sstw.p + sl.words);
+    sstw_keep_kernel<<<unsigned(sstw::grid_for(cap)), sstw::kThreads, 0, s>>>(
+        ok, reinterpret_cast<const unsigned long long*>(nblocks), status, cap, keep);
     KVSEP_HIP(hipGetLastError());
-    r = launch_batch_in(c, sc, s, capturing, file_base, off, sc.sst.p, nullptr, sc.sst.q, crc, first_bad,
-                        nbad, cap, n + cap, hint1);
+    // the salvage's layout and copy: a kept block's extent is its bytes and the 5-byte trailer that follows them
+    r = launch_offsets_in(sc, s,
+                          OffsetsCall{len, nullptr, keep, nullptr, 0, sstw::kTrailer, 0, ~uint64_t(0), dst_off,
+                                      words + sstw::kDataEnd, nkept ? nkept : words + sstw::kSalvaged, cap, cap});
     if (r) return r;
-    return launch_list(sc, s, capturing, crc, sc.sst.q, verdict_nbad(sc, first_bad, nbad),
-                       ListOut{bad_idx, bad_cap, ok}, cap);
+    r = launch_pack<PackPlain>(c, s,
+                               PackArgs{static_cast<const uint8_t*>(file_base), off,
+                                        reinterpret_cast<const uint64_t*>(sc.off.p), nullptr,
+                                        static_cast<uint8_t*>(dst), dst_bytes, dst_off, cap, cap, nullptr, nullptr, 0,
+                                        0});
+    if (r) return r;
+    return launch_sst_build_in(c, sc, s, capturing,
+                               SstBuildCall{file_base, key_off, key_len, dst_off, len, keep, cap, dst, dst_bytes,
+                                            words + sstw::kDataEnd, index_len, wstatus, table_bytes, status});
   });
 }
 

@@ -19,6 +19,7 @@
 #include "chain_run.h"
 #include "logw_run.h"
 #include "sst_run.h"
+#include "sstw_run.h"
 
 namespace kvsep {
 // crc32c_host.cpp: copies dst[i] <- src[i] (n[i] bytes) on the context's copier threads.
@@ -377,6 +378,82 @@ int kvsep_sst_index_walk(const char* blk, uint64_t blk_len, uint64_t* off, uint6
   for (uint64_t i = sst::held(total, cap); i < cap; ++i) off[i] = len[i] = 0;
   *nblocks = total;
   *status = code;
+  return KVSEP_OK;
+}
+
+int kvsep_sst_index_keys(const char* blk, uint64_t blk_len, uint64_t* off, uint64_t* len, uint64_t* key_off,
+                         uint64_t* key_len, uint64_t cap, uint64_t* nblocks, uint32_t* status) {
+  namespace sst = kvsep::sst;
+  if ((!blk && blk_len) || (cap && (!off || !len || !key_off || !key_len)) || !nblocks || !status)
+    return einval("kvsep_sst_index_keys: null argument");
+  const auto rd = [blk](uint64_t p) { return uint8_t(blk[p]); };
+  uint64_t total = 0;
+  uint32_t code = sst::kOk;
+  const sst::Tail t = sst::tail(rd, 0, blk_len);
+  if (!t.ok) code = sst::kBadRestarts;
+  for (uint64_t r = 0; !code && r < t.nrestarts; ++r) {  // the runs in order: the first error is the lowest run's
+    const sst::Run run = sst::run_of(rd, 0, t, r);
+    if (!run.ok) {
+      code = sst::kBadRestarts;
+      break;
+    }
+    const sst::Walked w = sst::walk_run_keys(
+        rd, 0, run, t.restart_offset, [&](uint64_t k, uint64_t o, uint64_t l, uint64_t kat, uint64_t klen) {
+          const uint64_t i = total + k;
+          if (i < cap) off[i] = o, len[i] = l, key_off[i] = kat, key_len[i] = klen;
+          return true;
+        });
+    total += w.count;
+    code = w.status;
+  }
+  for (uint64_t i = sst::held(total, cap); i < cap; ++i) off[i] = len[i] = key_off[i] = key_len[i] = 0;
+  *nblocks = total;
+  *status = code;
+  return KVSEP_OK;
+}
+
+int kvsep_sst_index_build(const char* key_base, const uint64_t* key_off, const uint64_t* key_len,
+                          const uint64_t* blk_off, const uint64_t* blk_len, const uint8_t* keep, uint64_t count,
+                          char* dst, uint64_t dst_bytes, uint64_t at, uint64_t* out_len, uint32_t* status) {
+  namespace sstw = kvsep::sstw;
+  if ((count && (!key_off || !key_len || !blk_off || !blk_len)) || !dst || !out_len || !status)
+    return einval("kvsep_sst_index_build: null argument");
+  if (count > 0xffffffffull) return einval("kvsep_sst_index_build: more than 2^32 - 1 entries");
+  const auto kept = [&](uint64_t i) { return sstw::kept(keep ? keep[i] : uint8_t(1), blk_off[i]); };
+  uint64_t entries = 0, nkept = 0;
+  for (uint64_t i = 0; i < count; ++i) {  // the totals first: a refusal writes nothing
+    entries = sstw::add_sat(entries, sstw::entry_size(kept(i), key_len[i], blk_off[i], blk_len[i]));
+    nkept += kept(i);
+  }
+  const sstw::Plan p = sstw::plan(entries, nkept, at, 0, 0, dst_bytes, 0);
+  *out_len = p.need;
+  *status = p.status;
+  if (p.status) return KVSEP_OK;
+  char* blk = dst + p.at;
+  uint64_t pos = 0, rank = 0;
+  for (uint64_t i = 0; i < count; ++i) {
+    if (!kept(i)) continue;
+    const uint64_t kl = key_len[i], size = sstw::entry_size(true, kl, blk_off[i], blk_len[i]);
+    const uint32_t h = sstw::head_len(kl);
+    for (uint64_t j = 0; j < size; ++j)
+      if (j < h || j >= h + kl) blk[pos + j] = char(sstw::frame_byte(j, kl, blk_off[i], blk_len[i]));
+    if (kl) memcpy(blk + pos + h, key_base + key_off[i], kl);
+    put_le32(blk + sstw::restart_at(entries, rank, i), uint32_t(pos));
+    pos += size;
+    ++rank;
+  }
+  if (sstw::lone_restart(nkept)) put_le32(blk + entries, 0);
+  put_le32(blk + sstw::count_at(entries, nkept), sstw::count_word(nkept));
+  const char type = 0;
+  const uint32_t masked = kvsep_crc32c_mask(kvsep_crc32c_extend_host(kvsep_crc32c_extend_host(0, blk, p.len), &type, 1));
+  for (uint32_t j = 0; j < sstw::kTrailer; ++j) blk[p.len + j] = char(sstw::trailer_byte(j, masked));
+  return KVSEP_OK;
+}
+
+int kvsep_sst_footer_build(uint64_t meta_off, uint64_t meta_len, uint64_t index_off, uint64_t index_len, char out[48]) {
+  if (!out) return einval("kvsep_sst_footer_build: null out");
+  for (uint32_t j = 0; j < kvsep::sstw::kFooter; ++j)
+    out[j] = char(kvsep::sstw::footer_byte(j, meta_off, meta_len, index_off, index_len));
   return KVSEP_OK;
 }
 

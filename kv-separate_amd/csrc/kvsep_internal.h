@@ -35,7 +35,7 @@ struct __attribute__((visibility("hidden"))) DevBuf {  // (no symbol of it leave
 };
 
 // Device scratch of one in-flight batch: the piece plan (planned mode), the work counter, the verify words and the
-// arrays of the SST, list, offsets, log, chains, log-frame and SST-index forms.  A scratch object is reused call after
+// arrays of the SST, list, offsets, log, chains, log-frame, SST-index and SST-build forms.  A scratch object is reused call after
 // call; `last_use` orders a call on a different stream behind the previous user, so reuse across streams is race-free
 // (crc32c_device.hip, with_scratch).  The host pipeline gives each staging slot its own Scratch so the two slots'
 // batches overlap, and every graph capture takes a capture set's Scratch of its own (stream_scratch).
@@ -57,10 +57,11 @@ struct Scratch {
   // log write side (crc32c_logframe.inc): a word per record | per fragment slot, per record / fragment slot
   DevBuf<uint32_t, kEvenEmpty, uint32_t> logw;
   DevBuf<unsigned long long, kEvenEmpty> sstidx;  // SST index walk (crc32c_sstindex.inc): sst::scratch_words, per run
+  DevBuf<unsigned long long, kEvenEmpty> sstw;    // SST index build (crc32c_sstbuild.inc): sstw::scratch_words, per entry
   template <typename F>
   void each_buf(F f) {  // every array above: what free_scratch frees
     f(plan_blocks), f(plan_pieces), f(scan_tmp), f(counter), f(verify), f(vslot), f(sst), f(tiles), f(off), f(log),
-        f(chain), f(logw), f(sstidx);
+        f(chain), f(logw), f(sstidx), f(sstw);
   }
   hipEvent_t last_use = nullptr;
   hipStream_t last_stream = nullptr;

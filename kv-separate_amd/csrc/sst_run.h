@@ -24,7 +24,7 @@ namespace sst {
 
 // ---- status codes (KVSEP_SST_* of the public header)
 constexpr uint32_t kOk = 0, kBadFooter = 1, kIndexChecksum = 2, kIndexCompressed = 3, kBadRestarts = 4, kBadEntry = 5,
-                   kBadHandle = 6, kCap = 7;
+                   kBadHandle = 6, kCap = 7, kSharedKey = 8;
 
 constexpr uint64_t kFooter = 48;                     // table/format.h: Footer::kEncodedLength
 constexpr uint64_t kMagicBytes = 8;
@@ -178,13 +178,15 @@ struct Entry {
   uint64_t next;     // block-relative offset of the entry after this one
   uint64_t key_len;  // shared + non_shared
   uint64_t off, len; // the handle in the value
+  uint64_t shared;   // key bytes taken from the entry before: 0 when the key is stored whole
+  uint64_t key_at;   // block-relative offset of the non_shared key bytes the entry stores (the whole key when shared == 0)
 };
 // The entry at block-relative p of a run that ends at `end` (p < end).  first: the run's first entry; prev_key: the key
-// length of the entry before it.  Keys are skipped, never read.
+// length of the entry before it.  Keys are skipped, never read: key_at is the position the decode steps over.
 template <class R = Rule, class Rd>
 KVSEP_HD Entry entry(Rd& rd, uint64_t base, uint64_t p, uint64_t end, uint64_t restart_offset, bool first,
                      uint64_t prev_key) {
-  const Entry bad{kBadEntry, 0, 0, 0, 0};
+  const Entry bad{kBadEntry, 0, 0, 0, 0, 0, 0};
   if (end - p < 3) return bad;
   uint32_t f[3] = {rd(base + p), rd(base + p + 1), rd(base + p + 2)};
   uint64_t q = p + 3;
@@ -202,29 +204,46 @@ KVSEP_HD Entry entry(Rd& rd, uint64_t base, uint64_t p, uint64_t end, uint64_t r
   if (!R::fits(non_shared + value_len, q, end, restart_offset)) return bad;
   const uint64_t vp = base + q + non_shared, vend = vp + value_len;
   const Var o = varint<64>(rd, vp, vend);
-  if (!o.ok) return {kBadHandle, 0, 0, 0, 0};
+  if (!o.ok) return {kBadHandle, 0, 0, 0, 0, 0, 0};
   const Var l = varint<64>(rd, o.next, vend);
-  if (!l.ok) return {kBadHandle, 0, 0, 0, 0};
-  return {kOk, q + non_shared + value_len, shared + non_shared, o.v, l.v};
+  if (!l.ok) return {kBadHandle, 0, 0, 0, 0, 0, 0};
+  return {kOk, q + non_shared + value_len, shared + non_shared, o.v, l.v, shared, q};
 }
 
 struct Walked {
   uint64_t count;   // entries before the run's end or its first error
   uint32_t status;  // that error
 };
-// One run: emit(k, off, len) for its k-th good entry; emit returns false to end the walk early (nothing more to store).
-template <class R = Rule, class Rd, class Emit>
-KVSEP_HD Walked walk_run(Rd& rd, uint64_t base, const Run& run, uint64_t restart_offset, Emit&& emit) {
+// The keys walk's extra rule.  Only a key stored whole has a contiguous place in the block: an entry with shared != 0 is
+// an error of its own, kSharedKey, under the same first-error rule (the reference writes index blocks at
+// block_restart_interval = 1, where shared is always 0).
+KVSEP_HD uint32_t key_status(const Entry& e) { return e.shared ? kSharedKey : kOk; }
+// One run, one loop for both walks: emit(k, off, len, key_at, key_len) for its k-th good entry; emit returns false to
+// end the walk early (nothing more to store).  kKeys: the keys walk, which also stops at key_status.
+template <bool kKeys, class R = Rule, class Rd, class Emit>
+KVSEP_HD Walked walk_run_as(Rd& rd, uint64_t base, const Run& run, uint64_t restart_offset, Emit&& emit) {
   uint64_t p = run.begin, k = 0, key = 0;
   while (p < run.end) {
     const Entry e = entry<R>(rd, base, p, run.end, restart_offset, k == 0, key);
     if (e.status) return {k, e.status};
-    if (!emit(k, e.off, e.len)) return {k + 1, kOk};
+    if (kKeys && key_status(e)) return {k, key_status(e)};
+    if (!emit(k, e.off, e.len, e.key_at, e.key_len)) return {k + 1, kOk};
     ++k;
     p = e.next;
     key = e.key_len;
   }
   return {k, kOk};
+}
+// The plain walk: emit(k, off, len).
+template <class R = Rule, class Rd, class Emit>
+KVSEP_HD Walked walk_run(Rd& rd, uint64_t base, const Run& run, uint64_t restart_offset, Emit&& emit) {
+  return walk_run_as<false, R>(rd, base, run, restart_offset,
+                               [&](uint64_t k, uint64_t o, uint64_t l, uint64_t, uint64_t) { return emit(k, o, l); });
+}
+// The keys walk: emit(k, off, len, key_at, key_len) also gets where the entry's key bytes lie in the block.
+template <class R = Rule, class Rd, class Emit>
+KVSEP_HD Walked walk_run_keys(Rd& rd, uint64_t base, const Run& run, uint64_t restart_offset, Emit&& emit) {
+  return walk_run_as<true, R>(rd, base, run, restart_offset, emit);
 }
 
 // ---- the count pass
@@ -259,18 +278,29 @@ KVSEP_HD uint32_t unmask(uint32_t m) {
 struct Counted {
   uint64_t cnt, err;
 };
-// Lane r of `runs` lanes.
-template <class R = Rule, class Rd>
-KVSEP_HD Counted count_lane(Rd& rd, uint64_t n, uint64_t ioff, uint64_t ilen, uint32_t pre, uint64_t runs,
-                            uint64_t r) {
+// Lane r of `runs` lanes, of either walk.
+template <bool kKeys, class R = Rule, class Rd>
+KVSEP_HD Counted count_lane_as(Rd& rd, uint64_t n, uint64_t ioff, uint64_t ilen, uint32_t pre, uint64_t runs,
+                               uint64_t r) {
   Tail t;
   const uint32_t whole = block_error(rd, n, ioff, ilen, pre, runs, &t);
   if (whole) return {0, r == 0 ? (whole | kWhole) : 0};
   if (r >= t.nrestarts) return {0, 0};
   const Run run = run_of(rd, ioff, t, r);
   if (!run.ok) return {0, kBadRestarts};
-  const Walked w = walk_run<R>(rd, ioff, run, t.restart_offset, [](uint64_t, uint64_t, uint64_t) { return true; });
+  const Walked w = walk_run_as<kKeys, R>(rd, ioff, run, t.restart_offset,
+                                         [](uint64_t, uint64_t, uint64_t, uint64_t, uint64_t) { return true; });
   return {w.count, w.status};
+}
+template <class R = Rule, class Rd>
+KVSEP_HD Counted count_lane(Rd& rd, uint64_t n, uint64_t ioff, uint64_t ilen, uint32_t pre, uint64_t runs,
+                            uint64_t r) {
+  return count_lane_as<false, R>(rd, n, ioff, ilen, pre, runs, r);
+}
+template <class R = Rule, class Rd>
+KVSEP_HD Counted count_lane_keys(Rd& rd, uint64_t n, uint64_t ioff, uint64_t ilen, uint32_t pre, uint64_t runs,
+                                 uint64_t r) {
+  return count_lane_as<true, R>(rd, n, ioff, ilen, pre, runs, r);
 }
 
 // ---- the stop
@@ -284,15 +314,28 @@ KVSEP_HD uint64_t keep_before(uint64_t stop, uint64_t err) {
 }
 
 // ---- the fill pass
-// Lane r with base[r] = b.  b == kSkip: the run is past the stop, and nothing of the image is read.
-template <class R = Rule, class Rd, class Emit>
-KVSEP_HD void fill_lane(Rd& rd, uint64_t ioff, uint64_t ilen, uint64_t r, uint64_t b, uint64_t limit, Emit&& emit) {
+// Lane r with base[r] = b, of either walk (emit as walk_run_as takes it).  b == kSkip: the run is past the stop, and
+// nothing of the image is read.
+template <bool kKeys, class R = Rule, class Rd, class Emit>
+KVSEP_HD void fill_lane_as(Rd& rd, uint64_t ioff, uint64_t ilen, uint64_t r, uint64_t b, uint64_t limit, Emit&& emit) {
   if (b == kSkip || b >= limit) return;
   const Tail t = tail(rd, ioff, ilen);
   if (!t.ok || r >= t.nrestarts) return;
   const Run run = run_of(rd, ioff, t, r);
   if (!run.ok) return;
-  walk_run<R>(rd, ioff, run, t.restart_offset, emit);
+  walk_run_as<kKeys, R>(rd, ioff, run, t.restart_offset, emit);
+}
+// The plain walk: emit(k, off, len).
+template <class R = Rule, class Rd, class Emit>
+KVSEP_HD void fill_lane(Rd& rd, uint64_t ioff, uint64_t ilen, uint64_t r, uint64_t b, uint64_t limit, Emit&& emit) {
+  fill_lane_as<false, R>(rd, ioff, ilen, r, b, limit,
+                         [&](uint64_t k, uint64_t o, uint64_t l, uint64_t, uint64_t) { return emit(k, o, l); });
+}
+// ... and the keys walk: emit(k, off, len, key_at, key_len).
+template <class R = Rule, class Rd, class Emit>
+KVSEP_HD void fill_lane_keys(Rd& rd, uint64_t ioff, uint64_t ilen, uint64_t r, uint64_t b, uint64_t limit,
+                             Emit&& emit) {
+  fill_lane_as<true, R>(rd, ioff, ilen, r, b, limit, emit);
 }
 
 // How many elements hold handles of data blocks: the count cut to the room for them.

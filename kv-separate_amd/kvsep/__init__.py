@@ -173,6 +173,20 @@ _SIGS = {
     "kvsep_sst_table_verify_device": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 6 +
                                       [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64] +
                                       [ctypes.c_void_p] * 3),
+    "kvsep_sst_index_keys": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 4 +
+                             [ctypes.c_uint64] + [ctypes.c_void_p] * 2),
+    "kvsep_sst_index_keys_device": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 5 +
+                                    [ctypes.c_uint64] + [ctypes.c_void_p] * 2),
+    "kvsep_sst_index_build": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                                                      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
+    "kvsep_sst_footer_build": (ctypes.c_int, [ctypes.c_uint64] * 4 + [ctypes.c_void_p]),
+    "kvsep_sst_index_build_device": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_uint64, ctypes.c_void_p,
+                                                                             ctypes.c_uint64] + [ctypes.c_void_p] * 3),
+    "kvsep_sst_table_finish_device": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_uint64, ctypes.c_void_p,
+                                                                              ctypes.c_uint64] + [ctypes.c_void_p] * 4),
+    "kvsep_sst_table_rewrite_device": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64, ctypes.c_void_p,
+                                                                               ctypes.c_uint64] + [ctypes.c_void_p] * 7 +
+                                       [ctypes.c_uint64, ctypes.c_uint64] + [ctypes.c_void_p] * 7),
     "kvsep_sst_trailers_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_uint64]),
     "kvsep_sst_verify_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
@@ -500,6 +514,60 @@ class Context:
                                                    _dptr(nblocks), _dptr(handles), _dptr(status)),
                "kvsep_sst_table_verify_device")
         return status
+
+    def sst_index_keys_device(self, file_base, n, handle, off, length, key_off, key_len, nblocks, status, cap=None,
+                              stream=None):
+        """kvsep_sst_index_keys_device: sst_index_device, and key_off / key_len (int64, cap elements): where each emitted
+        entry's key bytes lie in the image and how long they are.  An entry that shares key bytes with the one before
+        it stops the walk with SST_SHARED_KEY."""
+        if cap is None:
+            cap = min(int(off.numel()), int(length.numel()), int(key_off.numel()), int(key_len.numel()))
+        _check(lib().kvsep_sst_index_keys_device(self._h, _stream_handle(stream), _dptr(file_base), n, _dptr(handle),
+                                                 _dptr(off), _dptr(length), _dptr(key_off), _dptr(key_len), cap,
+                                                 _dptr(nblocks), _dptr(status)), "kvsep_sst_index_keys_device")
+        return nblocks
+
+    def sst_index_build_device(self, key_base, key_off, key_len, blk_off, blk_len, dst, dst_bytes, at, out_len, status,
+                               keep=None, count=None, stream=None):
+        """kvsep_sst_index_build_device: the index block BlockBuilder writes at restart interval 1 for the kept entries
+        (keep[i] != 0 and blk_off[i] != OFFSET_SKIP), with its trailer, at dst + at[0].  key_off / key_len / blk_off /
+        blk_len / at / out_len are int64 device tensors, keep uint8, status (one int32) a SSTW_* code."""
+        if count is None:
+            count = int(key_off.numel())
+        _check(lib().kvsep_sst_index_build_device(self._h, _stream_handle(stream), _dptr(key_base), _dptr(key_off),
+                                                  _dptr(key_len), _dptr(blk_off), _dptr(blk_len), _dptr(keep), count,
+                                                  _dptr(dst), dst_bytes, _dptr(at), _dptr(out_len), _dptr(status)),
+               "kvsep_sst_index_build_device")
+        return status
+
+    def sst_table_finish_device(self, key_base, key_off, key_len, blk_off, blk_len, dst, dst_bytes, data_end, index_len,
+                                table_bytes, status, keep=None, count=None, stream=None):
+        """kvsep_sst_table_finish_device: the empty metaindex block at dst + data_end[0], the index block of
+        sst_index_build_device after it, the footer after its trailer; table_bytes (one int64) the table's size."""
+        if count is None:
+            count = int(key_off.numel())
+        _check(lib().kvsep_sst_table_finish_device(self._h, _stream_handle(stream), _dptr(key_base), _dptr(key_off),
+                                                   _dptr(key_len), _dptr(blk_off), _dptr(blk_len), _dptr(keep), count,
+                                                   _dptr(dst), dst_bytes, _dptr(data_end), _dptr(index_len),
+                                                   _dptr(table_bytes), _dptr(status)), "kvsep_sst_table_finish_device")
+        return status
+
+    def sst_table_rewrite_device(self, file_base, n, dst, dst_bytes, off, length, key_off, key_len, crc, ok, dst_off,
+                                 nblocks, handles, status, index_len, table_bytes, wstatus, nkept=None, cap=None,
+                                 max_len_hint=0, stream=None):
+        """kvsep_sst_table_rewrite_device: the n-byte device table image at file_base without its bad blocks, as a
+        table, in dst: sst_table_verify_device with the keys walk, the salvage copy of the data blocks that passed, then
+        sst_table_finish_device with the new handles.  off / length / key_off / key_len / dst_off (int64), crc (int32)
+        and ok (uint8) have cap slots; status is the source's SST_* code, wstatus a SSTW_* code."""
+        if cap is None:
+            cap = min(int(t.numel()) for t in (off, length, key_off, key_len, crc, ok, dst_off))
+        _check(lib().kvsep_sst_table_rewrite_device(self._h, _stream_handle(stream), _dptr(file_base), n, _dptr(dst),
+                                                    dst_bytes, _dptr(off), _dptr(length), _dptr(key_off),
+                                                    _dptr(key_len), _dptr(crc), _dptr(ok), _dptr(dst_off), cap,
+                                                    max_len_hint, _dptr(nblocks), _dptr(nkept), _dptr(handles),
+                                                    _dptr(status), _dptr(index_len), _dptr(table_bytes),
+                                                    _dptr(wstatus)), "kvsep_sst_table_rewrite_device")
+        return wstatus
 
     def log_accept_gaps_device(self, base, n, off, length, type, ok, nrec, accept, gap=None, dropped=None,
                                bad_length=None, cap=None, stream=None):
@@ -954,6 +1022,9 @@ def log_walk(image):
 
 SST_OK, SST_BAD_FOOTER, SST_INDEX_CHECKSUM, SST_INDEX_COMPRESSED = 0, 1, 2, 3
 SST_BAD_RESTARTS, SST_BAD_ENTRY, SST_BAD_HANDLE, SST_CAP = 4, 5, 6, 7
+SST_SHARED_KEY = 8
+SSTW_OK, SSTW_TOO_LARGE, SSTW_NO_ROOM, SSTW_SOURCE = 0, 1, 2, 3
+OFFSET_SKIP = 0xFFFFFFFFFFFFFFFF
 
 
 def sst_footer(image):
@@ -981,6 +1052,58 @@ def sst_index_walk(block, cap=None):
     _check(lib().kvsep_sst_index_walk(p, keep.nbytes, off.ctypes.data_as(vp), ln.ctypes.data_as(vp), cap,
                                       ctypes.byref(nb), ctypes.byref(st)), "kvsep_sst_index_walk")
     return off[:cap], ln[:cap], nb.value, st.value
+
+
+def sst_index_keys(block, cap=None):
+    """sst_index_walk with keys (kvsep_sst_index_keys) -> (off, len, key_off, key_len, nblocks, status): key_off[i] /
+    key_len[i] say where entry i's key bytes lie in the block.  SST_SHARED_KEY at an entry that shares key bytes."""
+    p, keep = _buf(block)
+    vp = ctypes.c_void_p
+    nb, st = ctypes.c_uint64(), ctypes.c_uint32()
+    if cap is None:
+        _check(lib().kvsep_sst_index_keys(p, keep.nbytes, None, None, None, None, 0, ctypes.byref(nb),
+                                          ctypes.byref(st)), "kvsep_sst_index_keys")
+        cap = nb.value
+    a = [np.zeros(max(cap, 1), np.uint64) for _ in range(4)]
+    _check(lib().kvsep_sst_index_keys(p, keep.nbytes, *[x.ctypes.data_as(vp) for x in a], cap, ctypes.byref(nb),
+                                      ctypes.byref(st)), "kvsep_sst_index_keys")
+    return a[0][:cap], a[1][:cap], a[2][:cap], a[3][:cap], nb.value, st.value
+
+
+def sst_index_build(key_base, key_off, key_len, blk_off, blk_len, keep=None, dst=None, at: int = 0):
+    """The index block of the kept entries with its trailer (kvsep_sst_index_build) -> (bytes, out_len, status).
+    Without dst the block is sized first and returned on its own (block + 5 bytes; empty after a refusal); with dst (a
+    uint8 array) it is written at dst[at:] and dst is returned."""
+    p, hold = _buf(key_base)
+    vp = ctypes.c_void_p
+    arrs = [np.ascontiguousarray(x, np.uint64) for x in (key_off, key_len, blk_off, blk_len)]
+    count = len(arrs[0])
+    k = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+    ol, st = ctypes.c_uint64(), ctypes.c_uint32()
+
+    def call(d, nbytes, where):
+        _check(lib().kvsep_sst_index_build(p, *[x.ctypes.data_as(vp) for x in arrs],
+                                           None if k is None else k.ctypes.data_as(vp), count, d.ctypes.data_as(vp),
+                                           nbytes, where, ctypes.byref(ol), ctypes.byref(st)), "kvsep_sst_index_build")
+
+    if dst is not None:
+        call(dst, dst.nbytes, at)
+        return dst, ol.value, st.value
+    probe = np.zeros(1, np.uint8)
+    call(probe, 0, 0)  # no room: *out_len is the needed length
+    if st.value != SSTW_NO_ROOM:
+        return b"", ol.value, st.value
+    out = np.zeros(ol.value + 5, np.uint8)
+    call(out, out.nbytes, 0)
+    return out.tobytes(), ol.value, st.value
+
+
+def sst_footer_build(meta, index) -> bytes:
+    """Footer::EncodeTo (kvsep_sst_footer_build): meta / index = (off, len) -> the 48 bytes."""
+    out = np.zeros(48, np.uint8)
+    _check(lib().kvsep_sst_footer_build(meta[0], meta[1], index[0], index[1], out.ctypes.data_as(ctypes.c_void_p)),
+           "kvsep_sst_footer_build")
+    return out.tobytes()
 
 
 def log_accept(off, ok, n: int):

@@ -440,6 +440,8 @@ class Workgroup:
                  's_load_dwordx16': 16}[op]
             base = w.sget(o[1], 64) & ~3
             off = w.sget(o[2]) if len(o) > 2 else 0
+            if 'offset' in k.mods:  # the form with an SGPR offset and an immediate one: both are added
+                off += int(k.mods['offset'], 0)
             data = self.mem.read(base + off, 4 * n)
             vals = struct.unpack('<%dI' % n, data)
             m = REG.match(o[0])
@@ -759,6 +761,24 @@ class Workgroup:
                 self.lds[ad:ad + 4 * n] = np.frombuffer(
                     struct.pack('<%dI' % n, *[int(w.v[first + i][l]) for i in range(n)]), dtype=np.uint8)
             return
+        if op in ('ds_write_b8', 'ds_write_b16', 'ds_read_u8', 'ds_read_u16'):  # the table writer's byte staging
+            nb = 1 if op.endswith('8') else 2
+            wr = op.startswith('ds_write')
+            a = w.vget(o[0] if wr else o[1]).astype(np.int64) + off
+            data = w.vget(o[1]) if wr else None
+            out = w.vget(o[0]).copy() if not wr else None
+            for l in np.nonzero(act)[0]:
+                ad = int(a[l])
+                if ad < 0 or ad + nb > self.lds.size:
+                    raise EmuError('line %d: LDS address 0x%x out of range' % (k.line, ad))
+                if wr:
+                    self.lds[ad:ad + nb] = np.frombuffer(int(data[l] & ((1 << (8 * nb)) - 1)).to_bytes(nb, 'little'),
+                                                         dtype=np.uint8)
+                else:
+                    out[l] = int.from_bytes(self.lds[ad:ad + nb].tobytes(), 'little')
+            if not wr:
+                w.vset(o[0], out)
+            return
         m = re.match(r'ds_(read|write)2(st64)?_b(32|64)$', op)
         if m:  # two elements at addr + offset0 * size and addr + offset1 * size (st64: * 64 * size)
             n = int(m.group(3)) // 32
@@ -1076,6 +1096,10 @@ class Workgroup:
         if base == 'v_mad_u32_u24':
             a, b, c = V(o[1]) & u(0xFFFFFF), V(o[2]) & u(0xFFFFFF), V(o[3])
             w.vset(o[0], ((a.astype(np.uint64) * b.astype(np.uint64) + c) & np.uint64(M32)).astype(np.uint32))
+            return
+        if base == 'v_xad_u32':  # (S0 ^ S1) + S2
+            r = (V(o[1]) ^ V(o[2])).astype(np.uint64) + V(o[3]).astype(np.uint64)
+            w.vset(o[0], (r & np.uint64(M32)).astype(np.uint32))
             return
         if base == 'v_lshl_add_u32':
             a, sh, b = V(o[1]), V(o[2]) & u(31), V(o[3])
