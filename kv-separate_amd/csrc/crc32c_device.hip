@@ -47,6 +47,7 @@
 #include "kvsep_testing.h"
 #include "kvsep_internal.h"
 #include "plan_size.h"
+#include "route.h"
 #include "concat_run.h"
 #include "pack_run.h"
 #include "offsets_run.h"
@@ -97,7 +98,9 @@ struct kvsep_crc32c_ctx {
   uint64_t piece_bytes = 128 * 1024;  // best of 32 KiB .. 1 MiB on configs 3a/3b/4
   bool piece_auto = true;             // smaller pieces for small batches (piece_for); off once set explicitly
   int dynamic = -1;  // -1 auto, 0 static, 1 guided
-  int kernel = 0;    // kvsep_crc32c_ctx_set_kernel: 0 auto (use_narrow), 1 wide only, 2-6 narrow when the hint allows
+  int kernel = 0;    // kvsep_crc32c_ctx_set_kernel, 0..8 (route::Kernel): 0 auto, 1 wide only, 2-8 narrow when the hint allows
+  // what a routing decision reads (route.h)
+  route::Settings settings() const { return {num_cus, piece_bytes, piece_auto, dynamic, route::Kernel(kernel)}; }
   uint32_t static_contig = 1;  // static schedule: contiguous runs (1) or round-robin items (0, set_schedule(2))
   Scratch sc;  // scratch of the calls made directly on this context (any stream, event-ordered)
   std::vector<std::unique_ptr<CaptureSet>> caps;  // scratch of captured calls, one set per graph capture
@@ -381,115 +384,10 @@ int ensure_plan(Scratch& sc, uint64_t count, uint64_t pieces, bool capturing = f
   return rc;
 }
 
-// Narrow or wide kernel for an unsplit batch (every block <= piece_bytes, known from the max_len hint)?  The
-// narrow kernel's unit of parallelism is an 8-block group, so it needs many blocks; it wins on short blocks
-// when there are enough of them (measured, tools/ab_variants.py on one MI355X):
-//   <= 8 KiB blocks from 8 Ki blocks up (8 Ki x 4 KiB: 2.58 vs 2.13 TB/s; 4 Ki x 4 KiB: wide 1.50 vs 1.46),
-//   <= 16 KiB blocks from 16 Ki blocks up (16 Ki x 16 KiB: 5.58 vs 5.36; 4 Ki x 16 KiB: wide 3.67 vs 2.58),
-//   <= 32 KiB blocks from 32 Ki blocks up (32 Ki x 32 KiB: 6.72 vs 6.35; 16 Ki x 32 KiB: wide 6.12 vs 6.06),
-//   64 KiB blocks never (16 Ki x 64 KiB: wide 6.22 vs 4.88).
-// The thresholds scale with the CU count (256 on MI355X).  kvsep_crc32c_ctx_set_kernel can force either kernel
-// (tests); the choice never changes a result: both are exact for any block, whatever the hint.
-// A ragged batch: the max_len hint above 1.25x the mean length total_bytes / count (0 = unknown: not ragged).
-bool ragged_batch(uint64_t count, uint64_t total_bytes, uint64_t max_len) {
-  return count != 0 && total_bytes != 0 && 4 * max_len > 5 * (total_bytes / count);
-}
-
-// The claim kernel with 16-lane slots (form 11: 4-block groups of Z_256 rows) for uniform blocks of 8-12 KiB, from 4 Ki
-// of them up to 512 MiB.  Its groups are half the bytes of the 8-lane form's, so the waves' last groups end closer
-// together.  Measured against the routing before it in one process (profiles/round4/claim_shapes/claim16*.log, graph
-// replay, two boxes): 8 KiB blocks 32 MiB 11.05 vs 11.70 us, 64 MiB 15.73 vs 16.81, 128 MiB 23.94 / 24.14 vs 25.49 /
-// 25.29, 256 MiB 41.73 / 42.08 vs 43.78 / 44.08, 512 MiB 80.43 / 80.45 vs 81.73 / 82.07 (1 GiB equal); 10 KiB 64 MiB
-// 14.15 vs 19.89, 128 MiB 24.85 vs 31.30, 256 MiB 44.76 vs 44.13, 512 MiB 80.48 vs 82.61; 12 KiB 64 MiB 15.84 vs
-// 17.48, 128 MiB 28.88 / 28.12 vs 29.51 / 30.17, 256 MiB 46.01 / 45.68 vs 52.99 / 53.16, 512 MiB 90.06 / 89.33 vs
-// 93.73 / 93.18.  Outside that box it loses: 2 KiB and 6-7 KiB blocks at most sizes, 14-32 KiB blocks, 1 GiB.
-bool claim16_route(uint64_t count, uint64_t total_bytes, uint64_t max_len) {
-  const uint64_t bytes = total_bytes ? total_bytes : count * max_len;
-  return max_len >= 8 * 1024 && max_len <= 12 * 1024 && count >= 4096 && bytes <= (512ull << 20);
-}
-
-// Narrow-kernel form of a batch that use_narrow() put on the narrow kernels: 6 = 16-wave workgroups, 9 = 8-wave
-// workgroups (fill overlapped with the first loads), 10 = workgroup-contiguous runs dealt by LDS claims
-// (crc32c_narrow_claim_kernel, 8 waves), 11 = the same with 16-lane slots, 20 = sorted windows
-// (crc32c_narrow_sorted_kernel, 16 waves), 12 = the workgroup's 8 waves on one group (crc32c_narrow_coop_kernel;
-// set_kernel only: measured 1.5x the claim kernel's time on config 2, see its header).
-int narrow_form(const kvsep_crc32c_ctx* c, uint64_t count, uint64_t total_bytes, uint64_t max_len) {
-  if (c->kernel == 3) return 6;
-  if (c->kernel == 4) return 9;
-  if (c->kernel == 5) return 20;
-  if (c->kernel == 6) return 10;
-  if (c->kernel == 7) return 11;
-  if (c->kernel == 8) return 12;
-  // 16-wave workgroups below 128 Ki blocks of <= 8 KiB (32 Ki blocks of 8-32 KiB), 8-wave ones from there on.  A
-  // small batch gives each wave only a couple of 8-block groups, and more waves hide more of the launch/first-load
-  // ramp (256 MiB of 4 KiB blocks: 16 waves +2-5 %); a large one streams better with 8 (1 GiB of 4 KiB blocks:
-  // +5 %; 32 Ki x 16 KiB +2 %, 32 Ki x 32 KiB +6 %).  The 8-wave kernel overlaps the LDS fill with the first
-  // group's loads (+0.3-2 %); at 16 waves that overlap measured -5 %.
-  // Ragged batches take the sorted-window kernel at any size: an 8-block group waits for its longest block, and
-  // sorting 64-block windows by length makes the groups even (config 4's 902 K blocks <= 32 KiB: 0.93 -> 0.57 ms
-  // against the 16-wave narrow kernel, 1.24 ms on the 8-wave one).
-  if (ragged_batch(count, total_bytes, max_len)) return 20;
-  if (claim16_route(count, total_bytes, max_len)) return 11;
-  // The claim kernel (crc32c_narrow_claim_kernel) for uniform blocks of <= 8 KiB from 32 Ki of them up to 384 Ki of
-  // <= 4 KiB (128 MiB - 1.5 GiB of 4 KiB blocks) or 64 Ki of 4-8 KiB.  Measured against both forms below in one
-  // process (profiles/round4/queue_variants/claim_*.log, graph replay): 4 KiB blocks 128 MiB 26.8 vs 27.8 us, 256 MiB
-  // 45.9 vs 48.3, 512 MiB 83.1 vs 91.0, 1 GiB 156.7 vs 166.6, 1.5 GiB 241.4 vs 252.9, but 2 GiB 347.6 vs 314.0 (the
-  // wave-major 8-wave kernel streams better from there); 2 KiB blocks 256 MiB 44.9 vs 47.6, 1 GiB 165.1 vs 163.8;
-  // 8 KiB blocks 256 MiB 45.2 vs 45.8, 1 GiB 156.9 vs 155.0; 16 KiB blocks never (256 MiB 50.1 vs 44.0).
-  if (max_len <= 8 * 1024 && count >= (1u << 15) && count <= (max_len <= 4 * 1024 ? 3u << 17 : 1u << 16)) return 10;
-  const bool eight_waves = max_len <= 8 * 1024 ? count >= (1u << 17) : count >= (1u << 15);
-  return eight_waves ? 9 : 6;
-}
-
-// The claim kernel's shipped levers (crc32c_narrow_claim_kernel's kLean, round 6): the fill fetching each table entry
-// once and no head / tail loads for groups without such chunks -- 16 of config 2's 52 non-payload loads per wave.  On
-// one MI355X, interleaved in one process against the round-5 form (diag variant 65; tools/narrow_variants_probe.py,
-// profiles/round6/claim_lean.log): 4 KiB blocks 128 MiB 24.66 vs 24.88 us, 256 MiB 43.93 vs 44.32, 1 GiB 153.98 vs
-// 154.06 -- about 1 % at config 2, the time the loads cost; the rest of config 2's distance to the streaming read is not
-// in instruction count.  Bit 2 (no init load for init-less batches) measured nothing and is not shipped.
-constexpr uint32_t kClaimLean = 3;
-
-bool use_narrow(const kvsep_crc32c_ctx* c, uint64_t count, uint64_t total_bytes, uint64_t max_len) {
-  if (max_len == 0 || max_len > 2 * kNarrowMax) return false;
-  if (c->kernel == 1) return false;
-  if (c->kernel >= 2) return true;
-  const int d = diag_use_narrow(c);  // KVSEP_DIAG build only: -1 (no override) in the shipped library
-  if (d >= 0) return d != 0;
-  if (claim16_route(count, total_bytes, max_len) && !ragged_batch(count, total_bytes, max_len)) return true;
-  const uint64_t cus = uint64_t(c->num_cus);
-  return (max_len <= 8 * 1024 && count >= 32 * cus) || (max_len <= 16 * 1024 && count >= 64 * cus) ||
-         (max_len <= kNarrowMax && count >= 128 * cus);
-}
-
-static_assert(kWgThreads / 64 == kPlanWavesPerWg, "plan_size.h sizes plans for the default CRC workgroup");
-
-// What a batch call runs as: split into pieces through a plan or not, the piece size and its table (plan::piece_for:
-// smaller pieces for small batches under the default setting), and the schedule.  launch_batch_body runs what this
-// says and kvsep_crc32c_plan_query reports it.
-struct Route {
-  bool planned;
-  uint64_t piece_bytes;
-  const uint32_t* zpiece;
-  bool dyn;
-};
-
-Route route_batch(const kvsep_crc32c_ctx* c, uint64_t count, uint64_t total_bytes, uint64_t max_len) {
-  Route r;
-  r.planned = !(max_len != 0 && max_len <= c->piece_bytes);
-  r.piece_bytes = c->piece_bytes;
-  r.zpiece = &c->d_tabs->zpiece[0][0];
-  if (r.planned) {
-    const plan::Piece p = plan::piece_for(c->piece_bytes, c->piece_auto, c->num_cus, total_bytes);
-    r.piece_bytes = p.bytes;
-    if (p.table >= 0) r.zpiece = &c->d_tabs->zsmall[p.table][0][0];
-  }
-  // auto schedule: guided (one atomic per grab) for planned batches with many pieces; static for the rest --
-  // a few thousand small pieces would spend most of the kernel in single-item grabs on one counter
-  // (~88 dequeues/us, MI355X_MICROARCH.md dequeue)
-  const uint64_t est_items = r.planned ? count + total_bytes / r.piece_bytes : count;
-  const uint64_t nwaves_est = uint64_t(c->num_cus) * (kWgThreads / 64);
-  r.dyn = c->dynamic < 0 ? (r.planned && est_items >= 8 * nwaves_est) : c->dynamic == 1;
-  return r;
+// What a batch call runs as (route.h): the decision is made there, from the context's settings alone, and the launch,
+// ensure_plan_for, kvsep_crc32c_plan_query and kvsep_crc32c_kernel_name all read this one Route.
+route::Route route_of(const kvsep_crc32c_ctx* c, uint64_t count, uint64_t total_bytes, uint64_t max_len) {
+  return route::decide(c->settings(), count, total_bytes, max_len, diag_narrow(c));  // (KVSEP_DIAG build only: KVSEP_NARROW)
 }
 
 hipEvent_t take_event(kvsep_crc32c_ctx* c) {
@@ -536,6 +434,28 @@ void launch_pieces(const kvsep_crc32c_ctx* c, bool planned, bool dyn, bool verif
                    const PiecesArgs& a) {
   if (verify) launch_pieces_vv<true>(c, planned, dyn, grid, s, a);
   else launch_pieces_vv<false>(c, planned, dyn, grid, s, a);
+}
+
+// The narrow forms (route.h), each with its verify form; `threads` is the route's, the template's own workgroup.
+template <bool V>
+void launch_narrow_v(route::Form form, bool init, unsigned grid, unsigned threads, hipStream_t s, const PiecesArgs& a) {
+  using route::Form;
+  switch (form) {
+    case Form::Narrow8: crc32c_narrow_kernel<4, true, 512, true, true, LdsFull, V><<<grid, threads, 0, s>>>(a); break;
+    case Form::Claim: crc32c_narrow_claim_kernel<4, 512, V, true, 8, kClaimLean><<<grid, threads, 0, s>>>(a); break;
+    case Form::Claim16: crc32c_narrow_claim_kernel<4, 512, V, true, 16><<<grid, threads, 0, s>>>(a); break;
+    case Form::Coop:
+      if (init) crc32c_narrow_coop_kernel<V, true><<<grid, threads, 0, s>>>(a);
+      else crc32c_narrow_coop_kernel<V, false><<<grid, threads, 0, s>>>(a);
+      break;
+    case Form::Sorted: crc32c_narrow_sorted_kernel<4, true, 1024, V><<<grid, threads, 0, s>>>(a); break;
+    default: crc32c_narrow_kernel<4, true, 1024, false, true, LdsFull, V><<<grid, threads, 0, s>>>(a); break;
+  }
+}
+
+void launch_narrow(const route::Route& r, bool verify, bool init, unsigned grid, hipStream_t s, const PiecesArgs& a) {
+  if (verify) launch_narrow_v<true>(r.form, init, grid, r.threads, s, a);
+  else launch_narrow_v<false>(r.form, init, grid, r.threads, s, a);
 }
 
 int launch_batch_in(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capturing, const void* base,
@@ -619,9 +539,9 @@ int with_scratch(kvsep_crc32c_ctx* c, hipStream_t s, Scratch& eager, Needs needs
 // The plan of a checksum step inside a larger call, when its route takes one: sized with the call's other needs.
 int ensure_plan_for(kvsep_crc32c_ctx* c, Scratch& sc, uint64_t count, uint64_t total_bytes, uint64_t max_len,
                     bool capturing) {
-  const Route r = route_batch(c, count, total_bytes, max_len);
+  const route::Route r = route_of(c, count, total_bytes, max_len);
   if (!r.planned) return KVSEP_OK;
-  return ensure_plan(sc, count, plan::pieces_needed(r.piece_bytes, count, total_bytes), capturing);
+  return ensure_plan(sc, count, r.pieces_needed, capturing);
 }
 
 int launch_batch(kvsep_crc32c_ctx* c, Scratch& eager, hipStream_t s, const void* base, const uint64_t* off,
@@ -678,7 +598,7 @@ int launch_batch_body(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capt
                       const void* base, const uint64_t* off, const uint64_t* len, const uint32_t* init,
                       const uint32_t* expect, uint32_t* out, uint64_t* first_bad, uint64_t* nbad, uint64_t count,
                       uint64_t total_bytes, uint64_t max_len) {
-  const Route route = route_batch(c, count, total_bytes, max_len);
+  const route::Route route = route_of(c, count, total_bytes, max_len);
   const bool planned = route.planned;
   a.base = static_cast<const uint8_t*>(base);
   a.off = off;
@@ -686,8 +606,8 @@ int launch_batch_body(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capt
   a.init = init;
   a.out = out;
   a.count = count;
-  a.piece_bytes = route.piece_bytes;
-  a.zpiece = planned ? route.zpiece : nullptr;
+  a.piece_bytes = route.piece.bytes;
+  a.zpiece = !planned ? nullptr : route.piece.table < 0 ? &c->d_tabs->zpiece[0][0] : &c->d_tabs->zsmall[route.piece.table][0][0];
   a.tabs = c->d_tabs;
   if (expect) {
     if (!first_bad || !nbad) {
@@ -703,9 +623,8 @@ int launch_batch_body(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capt
   a.expect = expect;
   a.first_bad = reinterpret_cast<unsigned long long*>(first_bad);
   a.nbad = reinterpret_cast<unsigned long long*>(nbad);
-  // The verify form's compare runs inside the CRC kernels (and the combine kernel for split blocks): `fused`.  Only
-  // the A/B variants of the KVSEP_DIAG tools build fall back to the separate verify_finish_kernel pass.
-  bool fused = true;
+  // The verify form's compare runs inside the CRC kernels (and the combine kernel for split blocks).  Only the narrow
+  // variants of the KVSEP_DIAG tools build fall back to a separate pass (crc32c_diag.inc: diag_verify_finish).
   if (count == 0) return KVSEP_OK;
   const bool dyn = route.dyn;
   a.static_contig = c->static_contig;
@@ -719,7 +638,7 @@ int launch_batch_body(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capt
   // The start-state words (pstart[0], the guided counter) are written by a kernel of the call, never by a memset node
   // (see crc32c_plan_count_kernel).
   if (planned) {
-    int rc = ensure_plan(sc, count, plan::pieces_needed(a.piece_bytes, count, total_bytes), capturing);
+    int rc = ensure_plan(sc, count, route.pieces_needed, capturing);
     if (rc) return rc;
     a.pstart = sc.plan_blocks.q;
     a.pblk = sc.plan_pieces.p;
@@ -747,45 +666,11 @@ int launch_batch_body(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capt
     e1 = take_event(c);
     if (e0 && e1) KVSEP_HIP(hipEventRecord(e0, s));
   }
-  if (!planned && use_narrow(c, count, total_bytes, max_len)) {
-    int nv = narrow_form(c, count, total_bytes, max_len);
-    nv = diag_narrow_form(c, nv);  // KVSEP_DIAG build only
-    a.hint = max_len;
-    if (nv == 12 && a.hint > kCoopMaxLen) a.hint = kCoopMaxLen;  // its rows cover 4 KiB; longer blocks take its wide path
-    if (expect && (nv == 6 || nv == 9 || nv == 10 || nv == 11 || nv == 12 || nv == 20)) {  // the shipped forms' verify
-      switch (nv) {
-        case 9: crc32c_narrow_kernel<4, true, 512, true, true, LdsFull, true><<<grid, 512, 0, s>>>(a); break;
-        case 10: crc32c_narrow_claim_kernel<4, 512, true, true, 8, kClaimLean><<<grid, 512, 0, s>>>(a); break;
-        case 11: crc32c_narrow_claim_kernel<4, 512, true, true, 16><<<grid, 512, 0, s>>>(a); break;
-        case 12:
-          if (init) crc32c_narrow_coop_kernel<true, true><<<grid, 512, 0, s>>>(a);
-          else crc32c_narrow_coop_kernel<true, false><<<grid, 512, 0, s>>>(a);
-          break;
-        case 20: crc32c_narrow_sorted_kernel<4, true, 1024, true><<<grid, 1024, 0, s>>>(a); break;
-        default: crc32c_narrow_kernel<4, true, 1024, false, true, LdsFull, true><<<grid, 1024, 0, s>>>(a); break;
-      }
-    } else {
-    // KVSEP_DIAG variants only (the shipped forms are 6, 9, 10, 11, 12 and 20): they post to the caller's words directly, from
-    // their own in-kernel compare or from verify_finish_kernel, so those words are set first
-    if (expect) {
-      KVSEP_HIP(hipMemsetAsync(first_bad, 0xff, 8, s));
-      KVSEP_HIP(hipMemsetAsync(nbad, 0, 8, s));
-    }
-    a.vslot = nullptr;  // (their compare posts to the caller's words, captured or not)
-    fused = !expect || diag_self_compare(nv);
-    if (!diag_launch_narrow(nv, grid, s, a, count))  // KVSEP_DIAG build only
-    switch (nv) {
-      case 9: crc32c_narrow_kernel<4, true, 512, true><<<grid, 512, 0, s>>>(a); break;
-      case 10: crc32c_narrow_claim_kernel<4, 512, false, true, 8, kClaimLean><<<grid, 512, 0, s>>>(a); break;
-      case 11: crc32c_narrow_claim_kernel<4, 512, false, true, 16><<<grid, 512, 0, s>>>(a); break;
-      case 12:
-        if (init) crc32c_narrow_coop_kernel<false, true><<<grid, 512, 0, s>>>(a);
-        else crc32c_narrow_coop_kernel<false, false><<<grid, 512, 0, s>>>(a);
-        break;
-      case 20: crc32c_narrow_sorted_kernel<4, true, 1024><<<grid, 1024, 0, s>>>(a); break;
-      default: crc32c_narrow_kernel<4, true, 1024><<<grid, 1024, 0, s>>>(a); break;
-    }
-    }
+  a.hint = route.hint;
+  if (route.form != route::Form::Wide) {
+    KVSEP_HIP(diag_verify_words(route, s, a));  // KVSEP_DIAG build only: a narrow variant's verdict words
+    if (!diag_launch_narrow(route, grid, s, a))  // KVSEP_DIAG build only: a narrow variant in place of the form
+      launch_narrow(route, expect != nullptr, init != nullptr, grid, s, a);
   } else {
     launch_pieces(c, planned, dyn, expect != nullptr, grid, s, a);
   }
@@ -800,24 +685,20 @@ int launch_batch_body(kvsep_crc32c_ctx* c, Scratch& sc, hipStream_t s, bool capt
     KVSEP_HIP(hipEventRecord(e1, s));
     c->ev_pending.emplace_back(e0, e1);
   }
-  const unsigned cgrid = unsigned(std::min<uint64_t>((count + 255) / 256, kCombineMaxGrid));
+  const unsigned cgrid = route.combine_grid;
   if (planned) {
     a.vslot_base = grid;  // a captured verify call: the combine kernel's slots follow the CRC kernel's
     if (expect) crc32c_combine_kernel<true><<<cgrid, 256, 0, s>>>(a);
     else crc32c_combine_kernel<false><<<cgrid, 256, 0, s>>>(a);
     KVSEP_HIP(hipGetLastError());
   }
-  if (expect && fused && a.vslot) {  // a captured verify call's verdict from its slots
-    verify_slots_reduce_kernel<<<1, 256, 0, s>>>(a.vslot, grid + (planned ? cgrid : 0u),
+  if (expect && a.vslot) {  // a captured verify call's verdict from its slots
+    verify_slots_reduce_kernel<<<1, 256, 0, s>>>(a.vslot, grid + cgrid,
                                                  reinterpret_cast<unsigned long long*>(first_bad),
                                                  reinterpret_cast<unsigned long long*>(nbad));
     KVSEP_HIP(hipGetLastError());
   }
-  if (expect && !fused) {
-    verify_finish_kernel<<<unsigned((count + 255) / 256), 256, 0, s>>>(
-        out, expect, count, reinterpret_cast<unsigned long long*>(first_bad), reinterpret_cast<unsigned long long*>(nbad));
-    KVSEP_HIP(hipGetLastError());
-  }
+  KVSEP_HIP(diag_verify_finish(route, s, a));  // KVSEP_DIAG build only: the verdict of a variant without a compare
   return KVSEP_OK;
 }
 }  // namespace
@@ -2319,22 +2200,17 @@ int kvsep_sst_verify_list_host(kvsep_crc32c_ctx* c, const char* file, uint64_t n
 
 const char* kvsep_crc32c_kernel_name(kvsep_crc32c_ctx* c, uint64_t count, uint64_t total_bytes, uint64_t max_len) {
   if (!c) return "";
-  const bool planned = !(max_len != 0 && max_len <= c->piece_bytes);
-  if (planned || !use_narrow(c, count, total_bytes, max_len)) return "crc32c_pieces_kernel";
-  const int nf = narrow_form(c, count, total_bytes, max_len);
-  return nf == 20 ? "crc32c_narrow_sorted_kernel"
-         : nf == 10 || nf == 11 ? "crc32c_narrow_claim_kernel"
-         : nf == 12             ? "crc32c_narrow_coop_kernel"
-                                : "crc32c_narrow_kernel";
+  std::lock_guard<std::mutex> g(c->mu);
+  return route::kernel_name(route_of(c, count, total_bytes, max_len).form);
 }
 
 int kvsep_crc32c_plan_query(kvsep_crc32c_ctx* c, uint64_t count, uint64_t total_bytes, uint64_t max_len,
                             uint64_t* piece_bytes, uint64_t* pieces_needed, int* guided) {
   if (!c) return set_err(KVSEP_EINVAL, "null ctx");
   std::lock_guard<std::mutex> g(c->mu);
-  const Route r = route_batch(c, count, total_bytes, max_len);
-  if (piece_bytes) *piece_bytes = r.piece_bytes;
-  if (pieces_needed) *pieces_needed = r.planned ? plan::pieces_needed(r.piece_bytes, count, total_bytes) : 0;
+  const route::Route r = route_of(c, count, total_bytes, max_len);
+  if (piece_bytes) *piece_bytes = r.piece.bytes;
+  if (pieces_needed) *pieces_needed = r.pieces_needed;
   if (guided) *guided = r.dyn ? 1 : 0;
   return KVSEP_OK;
 }

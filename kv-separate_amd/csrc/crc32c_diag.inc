@@ -416,8 +416,13 @@ bool diag_launch_pieces(const kvsep_crc32c_ctx* c, unsigned grid, hipStream_t s,
   return true;
 }
 
-// Narrow-kernel variants (KVSEP_NARROW): returns false for the shipped forms (6, 9, 20) and anything not listed.
-bool diag_launch_narrow(int nv, unsigned grid, hipStream_t s, const PiecesArgs& a, uint64_t count) {
+// Narrow-kernel variants (KVSEP_NARROW), in place of the route's form: returns false when the route names none --
+// the shipped rule, or a shipped form's own number (route.h: 6, 9, 10, 11, 20).  A number not listed runs the 16-wave
+// narrow kernel's batch form, as it always has.
+bool diag_launch_narrow(const route::Route& r, unsigned grid, hipStream_t s, const PiecesArgs& a) {
+  const int nv = r.variant;
+  const uint64_t count = a.count;
+  if (nv == route::kDiagNone) return false;
   switch (nv) {
     case 2: crc32c_narrow_kernel<4, true, 512><<<grid, 512, 0, s>>>(a); break;
     case 3: crc32c_narrow_kernel<4, true, 768><<<grid, 768, 0, s>>>(a); break;
@@ -491,7 +496,7 @@ bool diag_launch_narrow(int nv, unsigned grid, hipStream_t s, const PiecesArgs& 
     case 63: crc32c_narrow_claim_kernel<4, 512, false, true, 8, 3><<<grid, 512, 0, s>>>(a); break;
     case 64: crc32c_narrow_claim_kernel<4, 512, false, true, 8, 7><<<grid, 512, 0, s>>>(a); break;
     case 65: crc32c_narrow_claim_kernel<4, 512><<<grid, 512, 0, s>>>(a); break;  // the round-5 form (kLean 0)
-    default: return false;
+    default: crc32c_narrow_kernel<4, true, 1024><<<grid, 1024, 0, s>>>(a); break;
   }
   return true;
 }
@@ -511,22 +516,32 @@ void diag_forget(const kvsep_crc32c_ctx* c) {
   g_diag.erase(c);
 }
 
-// use_narrow override: KVSEP_NARROW=0 never, >= 2 always; -1 = the shipped rule
-int diag_use_narrow(const kvsep_crc32c_ctx* c) {
-  const int n = diag_state(c).narrow;
-  return !n ? 0 : n >= 2 ? 1 : -1;
-}
-
-// narrow variants: 2: always 8 waves; 3: 12 waves; 4 / 5: 8-row groups at 8 / 12 waves; 6: always 16 waves; 7: as 1;
-// 9: 8 waves, fill overlapped with the first loads; 20 / 21 / 22: sorted windows at 16 / 8 / 12 waves; the rest above
-int diag_narrow_form(const kvsep_crc32c_ctx* c, int nv) {
-  const int n = diag_state(c).narrow;
-  return n != 1 && n != 7 && c->kernel < 3 ? n : nv;
-}
+// KVSEP_NARROW, as route::decide takes it (route.h: 0 never narrow, 1 / 7 the shipped rule, a shipped form's number
+// that form, the rest the variants above).  Narrow variants: 2: always 8 waves; 3: 12 waves; 4 / 5: 8-row groups at
+// 8 / 12 waves; 6: always 16 waves; 9: 8 waves, fill overlapped with the first loads; 20 / 21 / 22: sorted windows at
+// 16 / 8 / 12 waves; the rest above
+int diag_narrow(const kvsep_crc32c_ctx* c) { return diag_state(c).narrow; }
 
 // the sorted-window variants that post first_bad / nbad themselves (kVIn 1, 3, 4, 6: compare + atomics); 25 (load
 // only) and 28 (a plain store of first_bad, no count) do not, so the verify call runs verify_finish_kernel for them
 bool diag_self_compare(int nv) { return nv == 24 || nv == 26 || nv == 27 || nv == 29; }
+
+// A verify call on a narrow variant: the variants post to the caller's words directly, captured or not, from their own
+// in-kernel compare or from verify_finish_kernel, so those words are set first and the call takes no verdict slots.
+// (These two memset nodes are the tools build's alone: no shipped route reaches them.)
+hipError_t diag_verify_words(const route::Route& r, hipStream_t s, PiecesArgs& a) {
+  if (r.variant == route::kDiagNone || !a.expect) return hipSuccess;
+  a.vslot = nullptr;
+  const hipError_t e = hipMemsetAsync(a.first_bad, 0xff, 8, s);
+  return e != hipSuccess ? e : hipMemsetAsync(a.nbad, 0, 8, s);
+}
+
+// ... and the separate compare pass for the variants that have none of their own
+hipError_t diag_verify_finish(const route::Route& r, hipStream_t s, const PiecesArgs& a) {
+  if (r.variant == route::kDiagNone || !a.expect || diag_self_compare(r.variant)) return hipSuccess;
+  verify_finish_kernel<<<unsigned((a.count + 255) / 256), 256, 0, s>>>(a.out, a.expect, a.count, a.first_bad, a.nbad);
+  return hipGetLastError();
+}
 
 // KVSEP_CRC_VARIANT 31-34: the read patterns with the fold chain (stream_fold_kernel) in place of the ceiling
 bool diag_stream_read(const kvsep_crc32c_ctx* c, hipStream_t s, uintptr_t sp, uint64_t n16, uint32_t* sink) {
@@ -546,15 +561,15 @@ bool diag_stream_read(const kvsep_crc32c_ctx* c, hipStream_t s, uintptr_t sp, ui
 namespace {
 inline void diag_env(kvsep_crc32c_ctx*) {}
 inline void diag_forget(const kvsep_crc32c_ctx*) {}
-inline int diag_use_narrow(const kvsep_crc32c_ctx*) { return -1; }
-inline int diag_narrow_form(const kvsep_crc32c_ctx*, int nv) { return nv; }
-inline bool diag_self_compare(int) { return false; }
+inline int diag_narrow(const kvsep_crc32c_ctx*) { return kvsep::route::kDiagNone; }
+inline hipError_t diag_verify_words(const kvsep::route::Route&, hipStream_t, kvsep::PiecesArgs&) { return hipSuccess; }
+inline hipError_t diag_verify_finish(const kvsep::route::Route&, hipStream_t, const kvsep::PiecesArgs&) { return hipSuccess; }
 inline bool diag_stream_read(const kvsep_crc32c_ctx*, hipStream_t, uintptr_t, uint64_t, uint32_t*) { return false; }
 template <bool P, bool D>
 inline bool diag_launch_pieces(const kvsep_crc32c_ctx*, unsigned, hipStream_t, const kvsep::PiecesArgs&) {
   return false;
 }
-inline bool diag_launch_narrow(int, unsigned, hipStream_t, const kvsep::PiecesArgs&, uint64_t) { return false; }
+inline bool diag_launch_narrow(const kvsep::route::Route&, unsigned, hipStream_t, const kvsep::PiecesArgs&) { return false; }
 }  // namespace
 
 #endif  // KVSEP_DIAG

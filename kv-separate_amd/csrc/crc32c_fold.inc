@@ -5,7 +5,7 @@
 
 // ------------------------------------------------------------------------------------------------
 // LDS image of one CRC workgroup (bytes).  160,768 B of the 163,840 B a gfx950 workgroup may own.
-constexpr int kWgThreads = 512;  // default CRC workgroup: 8 waves, 2 per SIMD (see launch_pieces_v)
+// (kWgThreads, the default CRC workgroup of 8 waves, is route.h's.)
 // [0, 128 KiB): Z_1024, 4 byte-tables x 256 entries x 32 lane copies (see fold1024)
 constexpr uint32_t kZ4Off = 131072;      // Z_4     (4 KiB)
 constexpr uint32_t kTreeOff = 135168;    // Z_16, Z_32, Z_64, Z_128, Z_256, Z_512 (6 x 4 KiB)

@@ -4,7 +4,7 @@
 // namespace kvsep, by crc32c_device.hip; DESIGN.md §3.2-3.3.
 
 // ------------------------------------------------------------------------------------------------
-// Narrow kernel for batches of many short blocks (use_narrow): a wavefront runs 8 blocks at once,
+// Narrow kernel for batches of many short blocks (route::decide in route.h): a wavefront runs 8 blocks at once,
 // kNarrowLanes = 8 lanes ("a slot") per block and rows of 128 B on the 128-B address grid (see nstage).  The wide
 // kernel pays a fixed cost per block (lane merge, 6-level lane tree, staging: ~230 of its ~313 VALU
 // instructions for a 4 KiB block, PMC SQ_INSTS_VALU); here the merge is a 3-level tree inside the slot and
@@ -14,8 +14,7 @@
 // 128-B lines, one per slot.
 constexpr int kNarrowLanes = 8;
 constexpr uint32_t kNarrowRow = 16u * kNarrowLanes;
-constexpr uint64_t kNarrowMax = 32 * 1024;  // longest block the narrow kernel is ever chosen for (use_narrow)
-constexpr uint64_t kCoopMaxLen = 4096;  // crc32c_narrow_coop_kernel: 8 waves x 4 rows of 128 B; longer blocks go wide
+// (kNarrowMax, the longest block these kernels are ever chosen for, and the coop form's kCoopMaxLen are route.h's.)
 
 template <int kG>
 struct NStaged {
@@ -353,7 +352,7 @@ __global__ void __launch_bounds__(kThreads) crc32c_narrow_kernel(PiecesArgs a) {
   Desc dn;  // descriptors of the next group to take
   bool deferred = false;  // wave-uniform: some block of this wave's run exceeded the hint
   VAcc vacc;              // the verify form's verdict of this wave
-  const uint32_t hint32 = uint32_t(a.hint);  // <= 64 KiB (use_narrow)
+  const uint32_t hint32 = uint32_t(a.hint);  // <= 64 KiB (route::decide)
   auto take = [&](uint64_t g, NItem& it, NStaged<kG>& st) {
     const bool in = g + slot < hi;
     const bool over = in && (dn.lenhi != 0 || dn.len > hint32);
@@ -440,7 +439,7 @@ __global__ void __launch_bounds__(kThreads) crc32c_narrow_kernel(PiecesArgs a) {
   if (kVerify) verify_publish<kWavesPerWg>(a, wave, vacc);
 }
 
-// Batches of short blocks up to ~1 GiB (narrow_form 10, round 4): the workgroup owns a contiguous run of 8-block
+// Batches of short blocks up to ~1 GiB (route::Form::Claim, form 10, round 4): the workgroup owns a contiguous run of 8-block
 // groups and deals it to its 8 waves through an LDS claim counter (one ds_add per group: lgkmcnt, never in the rows'
 // vmcnt stream), so the waves the memory system serves first take more of the run.  Otherwise the narrow kernel's
 // pipeline: a group's rows are staged inside the previous group's finish, and the group after that is claimed and its
@@ -455,7 +454,7 @@ __global__ void __launch_bounds__(kThreads) crc32c_narrow_kernel(PiecesArgs a) {
 // first HBM round trip runs under the fill (diag variant 59 = without: 4 KiB blocks 128 MiB 25.60 -> 24.84 us, 256 MiB
 // 44.75 -> 44.15, 512 MiB 81.83 -> 81.29, 1 GiB 156.09 -> 154.77; profiles/round4/claim_shapes/).
 // kL: lanes per slot -- 16 makes a group 4 blocks (Z_256 rows, the tree tables' Z_256 replicated; narrow form 11, see
-// claim16_route; diag variant 60 is the same kernel).
+// route::decide's claim16 rule; diag variant 60 is the same kernel).
 // kLean (round 6, VERDICT r5's config-2 levers): bit 0 the fill fetches each table entry once (fill_lds<kOnce>), bit 1
 // the head / tail loads only for groups that have a head or tail chunk (nstage<kSkipHT>), bit 2 no initial-register
 // load when the batch has no inits (a launch-uniform branch).
@@ -473,7 +472,7 @@ __global__ void __launch_bounds__(kThreads) crc32c_narrow_claim_kernel(PiecesArg
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uintptr_t dummy = reinterpret_cast<uintptr_t>(a.tabs);
   const uint64_t count = a.count;
-  const uint32_t hint32 = uint32_t(a.hint);  // <= 64 KiB (use_narrow)
+  const uint32_t hint32 = uint32_t(a.hint);  // <= 64 KiB (route::decide)
   // this workgroup's contiguous run of groups [run0, run1); group indices fit 32 bits (count < 2^32)
   const uint32_t groups = uint32_t((count + kPerGroup - 1) / kPerGroup);
   const uint32_t per_wg = (groups + gridDim.x - 1) / gridDim.x;
@@ -610,7 +609,7 @@ __device__ __forceinline__ void wave_sort64(uint32_t& key, uint32_t& idx, uint32
   }
 }
 
-// Ragged batches of short blocks (see launch_batch_in): the narrow kernel's 8-block groups, but formed from 64-block
+// Ragged batches of short blocks (see route::decide): the narrow kernel's 8-block groups, but formed from 64-block
 // windows sorted by length, so a group's 8 blocks are of similar length and its slots do not wait for one long
 // block.  Lane i holds the descriptor of block W + i of window W (loaded a window ahead); after the sort, group k's
 // slot s takes the block at sorted position 8k + s (two ds_bpermutes to find it, four to fetch its descriptor).
@@ -637,7 +636,7 @@ __global__ void __launch_bounds__(kThreads) crc32c_narrow_sorted_kernel(PiecesAr
   const uint64_t lo = (uint64_t(wave) * gridDim.x + blockIdx.x) * gper * kPerGroup;  // wave-major runs
   uint64_t hi = lo + gper * kPerGroup;
   if (hi > a.count) hi = a.count;
-  const uint32_t hint32 = uint32_t(a.hint);  // <= 64 KiB (use_narrow)
+  const uint32_t hint32 = uint32_t(a.hint);  // <= 64 KiB (route::decide)
   // window descriptor of block W + lane; len: the length, kOver (longer than the hint: deferred) or kPast (past hi)
   constexpr uint32_t kOver = 0xffffffffu, kPast = 0xfffffffeu;
   struct WDesc {  // (the initial register is loaded per group, a group ahead of its use: two VGPRs less)
@@ -784,7 +783,7 @@ __global__ void __launch_bounds__(kThreads) crc32c_narrow_sorted_kernel(PiecesAr
 //    combines one block per group.
 //  * The head register (bytes before the first 16-B boundary, from ~init) enters wave 0's row-0 chain as the pending
 //    word at h0 (nfinish's injection); a block with no rows gets it in its combining wave.
-//  * Blocks longer than the hint (clamped to kCoopMaxLen at launch; never trusted) are left out of the group and
+//  * Blocks longer than the hint (clamped to kCoopMaxLen by route::decide; never trusted) are left out of the group and
 //    checksummed by their combining wave with the wide kernel's machinery (stage / finish, 1 KiB rows), any length.
 // The barrier is `s_waitcnt lgkmcnt(0); s_barrier` only -- never a vmcnt wait: the next groups' rows stay in flight.
 // MEASURED, NOT ROUTED (set_kernel("coop") only).  Bit-exact everywhere (tools/coop_probe.py; the -m gpu suite's coop

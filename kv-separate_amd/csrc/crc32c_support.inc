@@ -5,8 +5,7 @@
 // One thread per block: Horner over the block's pieces, R <- Z_piece(R) ^ R_piece.  kVerify: also the verify form's
 // compare for the split blocks (the CRC kernel checked the whole ones).  A grid of at most kCombineMaxGrid workgroups
 // strides over the batch (round 6: a captured verify call keeps one verdict slot per workgroup, so the slot count is
-// bounded whatever the block count).
-constexpr uint32_t kCombineMaxGrid = 2048;
+// bounded whatever the block count).  route.h holds the constant and the grid rule.
 template <bool kVerify = false>
 __global__ void __launch_bounds__(256) crc32c_combine_kernel(PiecesArgs a) {
   __shared__ uint32_t zp[1024];

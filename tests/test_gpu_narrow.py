@@ -1,5 +1,5 @@
 """GPU parity of the narrow kernel (8 lanes per block, 8 blocks per wavefront), which serves unsplit batches
-of many short blocks (SST blocks, WAL fragments; routing rule use_narrow() in crc32c_device.hip), forced here
+of many short blocks (SST blocks, WAL fragments; routing rule route::decide in csrc/route.h), forced here
 for every batch whose max_len hint is <= 64 KiB.  Bit-exact vs the oracle restatement and
 vs the wide kernel (set_kernel("wide") context), on ragged lengths, any alignment, non-zero init, partial
 8-block groups and verify mode."""
@@ -143,7 +143,7 @@ def test_sorted_windows_ragged(oracle, pool, count):
         assert (fb.item(), nb.item()) == (bad[0], len(bad))
         assert np.array_equal(out.cpu().numpy().view(np.uint32), exp)
         ctx.set_kernel("auto")
-        n = 40000  # enough blocks for the narrow kernels (use_narrow); ragged -> sorted, uniform -> plain
+        n = 40000  # enough blocks for the narrow kernels (route::decide); ragged -> sorted, uniform -> plain
         assert ctx.kernel_name(n, 32768, n * 2000) == "crc32c_narrow_sorted_kernel"
         assert ctx.kernel_name(n, 4096, n * 4096) == "crc32c_narrow_claim_kernel"  # uniform, < 256 Ki blocks
         assert ctx.kernel_name(n, 4096) == "crc32c_narrow_claim_kernel"  # total_bytes unknown: not ragged

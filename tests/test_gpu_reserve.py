@@ -373,7 +373,7 @@ def cfg2_file(oracle):
 
 
 def cfg2_read_check_kernel(count):
-    """narrow_form (csrc/crc32c_device.hip) for the read check's call of uniform 4,097-byte blocks under a 4,097
+    """route::decide (csrc/route.h) for the read check's call of uniform 4,097-byte blocks under a 4,097
     hint: the claim kernel from 1 << 15 blocks up to 1 << 16 (the bound for max_len > 4 KiB), else the narrow kernel
     (16-wave below 1 << 17 blocks)."""
     return "crc32c_narrow_claim_kernel" if (1 << 15) <= count <= (1 << 16) else "crc32c_narrow_kernel"

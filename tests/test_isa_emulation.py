@@ -26,7 +26,7 @@ ASM = os.path.join(PKG, "build", "crc32c_device-hip-amdgcn-amd-amdhsa-gfx950.s")
 sys.path.insert(0, os.path.join(PKG, "tools"))
 sys.path.insert(0, PKG)
 
-# the shipped narrow-family templates (launch_batch_in in csrc/crc32c_device.hip): name, threads per workgroup.  The
+# the shipped narrow-family templates (launch_narrow_v in csrc/crc32c_device.hip): name, threads per workgroup.  The
 # claim kernel's waves take groups through an LDS counter; the emulator runs a workgroup's waves to each barrier in
 # order, so its deal differs from the hardware's (a different interleaving, the same set of groups)
 SORTED = "_ZN5kvsep27crc32c_narrow_sorted_kernelILi4ELb1ELi1024ELb%dENS_5ExactEEEvNS_10PiecesArgsE"

@@ -24,7 +24,7 @@ RES = os.path.join(BUILD, "resource.txt")
 sys.path.insert(0, os.path.join(PKG, "tools"))
 
 # kernel name fragment -> threads per workgroup of its launch (the caps follow: 4 SIMDs per CU, 512 VGPRs per lane
-# slot per SIMD): the shipped templates, see launch_pieces_v / launch_batch_in in csrc/crc32c_device.hip
+# slot per SIMD): the shipped templates, see launch_pieces_v / launch_narrow_v in csrc/crc32c_device.hip
 LAUNCH_THREADS = {
     "crc32c_pieces_kernel": 512,
     "crc32c_narrow_kernelILi4ELb1ELi512E": 512,
@@ -141,7 +141,7 @@ def test_shipped_kernels_are_exact_only(built):
                       "SortedVIn", "SortedDrain"):
         assert diag_type not in text, diag_type
     src = "".join(open(os.path.join(PKG, "csrc", f)).read() for f in (
-        "crc32c_device.hip", "crc32c_fold.inc", "crc32c_wide.inc", "crc32c_narrow.inc", "crc32c_support.inc"))
+        "crc32c_device.hip", "route.h", "crc32c_fold.inc", "crc32c_wide.inc", "crc32c_narrow.inc", "crc32c_support.inc"))
     for switch in ("kAbl", "kStrided", "kVIn", "c->variant", "c->narrow"):
         assert switch not in src, switch
     diag = open(os.path.join(PKG, "csrc", "crc32c_diag.inc")).read()
