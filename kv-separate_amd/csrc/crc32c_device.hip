@@ -1167,7 +1167,17 @@ int sst_verify_locked(kvsep_crc32c_ctx* c, void* stream, const void* file_base, 
         return rc;
       },
       [&](Scratch& sc, bool capturing) {
-        if (count) {
+        if (!count) {
+          // No handle: the verdict is "none", posted here.  launch_batch_in takes a call for a verify by its stored-word
+          // array, and a scratch that never held SST arrays has none for count 0.
+          if (first_bad || nbad) {
+            start_words_kernel<<<1, 64, 0, s>>>(nullptr, reinterpret_cast<unsigned long long*>(first_bad),
+                                                reinterpret_cast<unsigned long long*>(nbad));
+            KVSEP_HIP(hipGetLastError());
+          }
+          return KVSEP_OK;
+        }
+        {
           sst_verify_prep_kernel<<<unsigned((count + 255) / 256), 256, 0, s>>>(
               static_cast<const uint8_t*>(file_base), off, len, sc.sst.p, sc.sst.q, count);
           KVSEP_HIP(hipGetLastError());

@@ -19,6 +19,7 @@ import pytest
 import kvsep
 import framing_corpus as FC
 from framing_builders import FIRST, FULL, LAST, MIDDLE, assemble, fnv64
+from framing_builders import log_chain_table as table
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 CSRC = os.path.join(ROOT, "kv-separate_amd", "csrc")
@@ -82,36 +83,6 @@ def test_log_chains_on_the_recorded_corpus():
             assert nwhole == len(got) and (first[nchain:] == off.size).all() and not whole[nchain:].any(), what
             k += 1
     assert k == sum(len(v) for v in doc["classes"].values()) and k > 100
-
-
-def table(ty, accept, gap):
-    """The rule table of include/kvsep_crc32c.h, restated: (first, whole) with their padding."""
-    count = len(ty)
-    first, whole, state_in = [], [], False
-    continued = False
-    for i in range(count):
-        t, a, g = int(ty[i]), int(accept[i]), int(gap[i])
-        if not a:
-            cont, after = False, False
-        elif t == FIRST:
-            cont, after = False, True
-        elif t == MIDDLE and not g:
-            cont, after = state_in, state_in
-        elif t == MIDDLE:
-            cont, after = False, False
-        elif t == LAST:
-            cont, after = (not g) and state_in, False
-        else:
-            cont, after = False, False
-        if not cont:
-            first.append(i)
-            whole.append(0)
-        continued = cont
-        # the chain is whole iff its last record is an accepted FULL or a LAST that continued: the latest record decides
-        whole[-1] = 1 if a and (t == FULL or (t == LAST and continued)) else 0
-        state_in = after
-    nchain = len(first)
-    return first + [count] * (count + 1 - nchain), whole + [0] * (count - nchain), nchain
 
 
 def test_log_chains_against_the_table_on_random_triples():

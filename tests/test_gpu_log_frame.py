@@ -20,7 +20,7 @@ import pytest
 
 import kvsep
 import framing_corpus as FC
-from framing_builders import BLOCK, HEADER, FIRST, FULL, LAST, MIDDLE, fnv64, log_image
+from framing_builders import BLOCK, HEADER, FIRST, FULL, LAST, MIDDLE, fnv64, log_image, writer
 
 pytestmark = pytest.mark.gpu
 
@@ -44,35 +44,6 @@ def ctx():
     c = kvsep.Context(0)
     yield c
     c.close()
-
-
-def writer(lens, keep, dest_length):
-    """log::Writer::AddRecord (db/log_writer.cc:35-82) over the kept lengths, from block offset dest_length % 32768:
-    ([(header offset, type, fragment length, record, position in the record)], [(pad offset, pad bytes, record)],
-    bytes appended)."""
-    phys, pads, pos, block_off = [], [], 0, dest_length % BLOCK
-    for r, n in enumerate(lens):
-        if not keep[r]:
-            continue
-        left, at, begin = int(n), 0, True
-        while True:
-            leftover = BLOCK - block_off
-            if leftover < HEADER:
-                if leftover:
-                    pads.append((pos, leftover, r))
-                pos += leftover
-                block_off = 0
-            frag = min(left, BLOCK - block_off - HEADER)
-            end = left == frag
-            phys.append((pos, FULL if begin and end else FIRST if begin else LAST if end else MIDDLE, frag, r, at))
-            pos += HEADER + frag
-            block_off += HEADER + frag
-            at += frag
-            left -= frag
-            begin = False
-            if left == 0:
-                break
-    return phys, pads, pos
 
 
 class Frame:

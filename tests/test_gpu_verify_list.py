@@ -276,6 +276,34 @@ def test_sst_list_forms_name_the_damaged_blocks(ctx):
             assert nb2 == 3 and bad2.tolist() == want[:2]
 
 
+def test_sst_forms_post_the_verdict_of_no_handles_on_a_fresh_context():
+    """count == 0 on a context whose scratch never held SST arrays (found by the forms soak, lists/20261021/1): the
+    read check, its list form and the salvage write *first_bad = UINT64_MAX and *nbad = 0 as the verify form does; they
+    used to leave both words as they were there, and to write them on a context that had run an SST call before."""
+    c = kvsep.Context(0)
+    try:
+        d = torch.zeros(16, dtype=torch.uint8, device=DEV)
+        z = torch.zeros(1, dtype=torch.int64, device=DEV)  # off / len: never read
+        out = torch.zeros(1, dtype=torch.int32, device=DEV)
+        for form in ("verify", "list", "salvage"):
+            w = torch.full((4,), 0x5A5A5A5A, dtype=torch.int64, device=DEV)  # first_bad, nbad, end, nkept
+            if form == "verify":
+                c.sst_verify_device(d.data_ptr(), z, z, out, w[0:1], w[1:2], count=0, total_bytes=0)
+            elif form == "list":
+                c.sst_verify_list_device(d.data_ptr(), z, z, out, w[0:1], w[1:2], bad_idx=z, bad_cap=1, count=0,
+                                         total_bytes=0)
+            else:
+                ok = torch.zeros(1, dtype=torch.uint8, device=DEV)
+                c.sst_salvage_device(d.data_ptr(), z, z, out, ok, d, 16, z, w[2:3], first_bad=w[0:1], nbad=w[1:2],
+                                     nkept=w[3:4], count=0, total_bytes=0)
+            torch.cuda.synchronize()
+            assert w[:2].tolist() == [-1, 0], form
+            if form == "salvage":
+                assert w[2:].tolist() == [0, 0]
+    finally:
+        c.close()
+
+
 # ------------------------------------------------------------------------------------------------ log / MANIFEST
 def test_log_verify_device_matches_the_host_path(ctx, oracle):
     """A log image with records corrupted in two different 32 KiB blocks: ok[] from the device form equals

@@ -51,6 +51,8 @@ ASM = os.path.join(PKG, "build", "crc32c_device-hip-amdgcn-amd-amdhsa-gfx950.s")
 sys.path.insert(0, os.path.join(PKG, "tools"))
 sys.path.insert(0, PKG)
 
+from framing_builders import ref_offsets  # noqa: E402  (the serial offsets loop, shared with the forms soak)
+
 M64 = (1 << 64) - 1
 SKIP = M64
 FAR = 1 << 40  # an address no region of the emulated memory reaches
@@ -223,34 +225,7 @@ class Call:
         print("%-60s %9d wave-instructions" % (self.tag, self.steps))
 
 
-def sat(a, b):
-    return min(a + b, M64)
-
-
 # ===================================================================================================== offsets
-def ref_offsets(seg_len, first, keep, before, head, tail, start, max_size, count):
-    """dst_off, end, nkept by the serial loop of crc32c_offsets.inc's header comment."""
-    pos, nk, out, kept_segs = start, 0, [], set()
-    for i in range(count):
-        kept = (keep is None or keep[i] != 0) and (before is None or i < before)
-        if not kept:
-            out.append(SKIP)
-            continue
-        s, e = (int(first[i]), int(first[i + 1])) if first is not None else (i, i + 1)
-        size = 0
-        for j in range(s, e):
-            size = sat(size, int(seg_len[j]))
-            kept_segs.add(j)
-        if size > max_size:
-            size = M64
-        ext = sat(sat(head, size), tail)
-        end = sat(pos, ext)
-        out.append(end - ext if end != M64 else SKIP)
-        pos = end
-        nk += 1
-    return np.array(out, np.uint64), pos, nk, kept_segs
-
-
 def run_offsets(env, tag, seg_len, first, keep, before, head, tail, start, max_size, count, nkept_word=True):
     c = Call(env, tag)
     nseg = len(seg_len)
