@@ -13,6 +13,12 @@ Three layers; the first two need no GPU and never touch torch.cuda:
               every destination between 64 canary bytes; compare() checks every element, the guards and that the inputs
               are unchanged, and names the family, seed, case, array and index of the first difference.
 
+What the soak does not reach: a case holds at most MAX_ELEMENTS elements and MAX_PAYLOAD (8 MiB) of payload, so that it
+stays fast; every position it produces is far below 2^32 (a far `start` or dest_length enters as arithmetic only).
+Offsets and totals of 2^32 and over -- far seg_off / dst_off / rec_off, sums and payloads that pass 4 GiB, a log image
+over 4 GiB -- are covered by tests/test_gpu_far_offsets.py, which uses the models below, and by
+tests/test_isa_envelope_far.py on the shipped assembly.
+
 usage: soak_forms.py [--seconds 240] [--seed N] [--family F] [--case K]
 One line per case; exits non-zero on the first mismatch.  tests/test_gpu_soak_forms.py runs a fixed seeded slice,
 tests/test_soak_forms_cpu.py checks the models against the host forms, the generators' reach and the comparator."""

@@ -46,7 +46,14 @@ class Memory:
 
     def alloc(self, nbytes: int, align: int = 256, data=None, phase: int = 0, at: int = 0) -> int:
         """A region of nbytes whose base is `phase` past a multiple of `align`; data is copied in at byte `at`."""
-        base = (self.next - phase + align - 1) // align * align + phase
+        return self.alloc_at((self.next - phase + align - 1) // align * align + phase, nbytes, data, at)
+
+    def alloc_at(self, base: int, nbytes: int, data=None, at: int = 0) -> int:
+        """A region of nbytes at the address `base`: a window at a large offset from another region or from an address
+        that is mapped nowhere (a kernel's `base` argument), without the span between them -- an access that falls
+        short of the window is a bad address.  The region must not touch one that exists."""
+        if any(base < b + a.size and b < base + max(1, nbytes) for b, a in self.regions):
+            raise EmuError("alloc_at 0x%x (+%d) overlaps a region" % (base, nbytes))
         arr = np.zeros(max(1, nbytes), dtype=np.uint8)
         if data is not None:
             b = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else \
@@ -55,7 +62,7 @@ class Memory:
         self.regions.append((base, arr))
         if self.marks is not None:
             self.marks[base] = (np.zeros(arr.size, dtype=bool), np.zeros(arr.size, dtype=bool))
-        self.next = base + arr.size + 4096
+        self.next = max(self.next, base + arr.size + 4096)
         return base
 
     def find(self, addr: int, n: int):
