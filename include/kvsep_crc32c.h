@@ -47,7 +47,8 @@ extern "C" {
  * kvsep_log_frame_device) and the SST table reader (kvsep_sst_footer, kvsep_sst_index_walk, kvsep_sst_index_device,
  * kvsep_sst_table_verify_device, the KVSEP_SST_* status codes) and the SST table writer (kvsep_sst_index_keys,
  * kvsep_sst_index_keys_device, kvsep_sst_index_build, kvsep_sst_footer_build, kvsep_sst_index_build_device,
- * kvsep_sst_table_finish_device, kvsep_sst_table_rewrite_device, KVSEP_SST_SHARED_KEY, the KVSEP_SSTW_* status codes).
+ * kvsep_sst_table_finish_device, kvsep_sst_table_rewrite_device, KVSEP_SST_SHARED_KEY, the KVSEP_SSTW_* status codes)
+ * and the device value-log reader (kvsep_vlog_walk_device, kvsep_vlog_read_device).
  * The reference's C++ symbol leveldb::crc32c::Extend is not in this library: it is in the libkvsep_leveldb_abi.so
  * shim. */
 #define KVSEP_ABI_VERSION 4
@@ -379,6 +380,41 @@ int kvsep_log_accept_gaps_device(kvsep_crc32c_ctx* ctx, void* stream, const void
 int kvsep_log_read_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, uint64_t n, uint64_t* off,
                           uint64_t* len, uint32_t* stored, uint8_t* type, uint8_t* ok, uint8_t* accept, uint8_t* gap,
                           uint64_t cap, uint64_t* nrec, uint64_t* dropped, uint64_t* bad_length_bytes);
+
+/* ---------------------------------------------------------------- value-log reader on the device
+ * kvsep_vlog_walk and the totals of kvsep_vlog_verify_host for a vlog image that is on the device (the output of
+ * kvsep_vlog_frame_auto_device, say), so that walk -> checksum -> verdict runs on one stream with no host step and can
+ * be captured.  vlog records lie back to back, so the position of each header is known only from the one before it: one
+ * wavefront follows the chain through a window of the image staged in LDS, a global round trip per window instead of
+ * per record.  An image of very many tiny records is therefore one wavefront for a long time (known bad
+ * cases).  ABI 4 gained them as new entry points only.
+ * Every array is a DEVICE pointer; every call is asynchronous on `stream`; no atomics.  Refused with KVSEP_EINVAL
+ * before any device is touched: a null ctx, a null base with n != 0, a null nrec, cap > 2^32 - 1, and in the read form
+ * a null off / len / stored / crc with cap != 0.
+ * Memory touched: the image is never written; it is read in naturally aligned 16-byte granules that each hold at least
+ * one byte of [base, base + n), whatever the alignment of base; with n == 0 base is not dereferenced. */
+/* The walk.  *nrec (a device word, required) and *consumed (nullable) = what kvsep_vlog_walk(buf, n, ...) returns and
+ * writes for the same bytes.  off / len / stored are each nullable and each written for exactly cap elements: element
+ * i < min(*nrec, cap) holds what the host walk gives for record i; every element from there to cap is padding, off =
+ * len = 0 and stored = kvsep_crc32c_mask(0), an empty block that passes kvsep_crc32c_verify_device(count = cap) and is
+ * never dereferenced there.  cap == 0 with null arrays is the counting call; *nrec > cap says the arrays were cut.  Like
+ * the host walk it does not stop at a bad checksum.  One kernel, no scratch: it can always be captured. */
+int kvsep_vlog_walk_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, uint64_t n, uint64_t* off,
+                           uint64_t* len, uint32_t* stored, uint64_t cap, uint64_t* nrec, uint64_t* consumed);
+/* The whole reader: the walk, kvsep_crc32c_verify_device(count = cap, total_bytes = n, max_len = max_len_hint ?
+ * max_len_hint : n) with expected_masked = stored and out = crc, the ok[] pass of kvsep_crc32c_verify_list_device when
+ * ok (cap bytes, nullable) is given, and the totals, chained on `stream` with no host step.  off, len, stored and crc
+ * are required when cap != 0.  *first_bad / *nbad (nullable) are the verify call's words: the padding passes, so they
+ * speak of records only.  With c = min(*nrec, cap) and g = the leading records among the first c that pass, the
+ * nullable device words receive *ngood = g, *good_bytes = g ? off[g-1] + len[g-1] : 0 and *drop_bytes = g < c ? len[g]
+ * : 0 -- with *nrec <= cap exactly kvsep_vlog_verify_host's outputs.
+ * Scratch: what the checksum step needs.  After kvsep_crc32c_reserve(ctx, count >= cap, total_bytes >= n) the call
+ * allocates nothing and can be captured; a captured call larger than the reservation fails with KVSEP_EINVAL before
+ * anything is enqueued. */
+int kvsep_vlog_read_device(kvsep_crc32c_ctx* ctx, void* stream, const void* base, uint64_t n, uint64_t* off,
+                           uint64_t* len, uint32_t* stored, uint32_t* crc, uint8_t* ok, uint64_t cap,
+                           uint64_t max_len_hint, uint64_t* nrec, uint64_t* consumed, uint64_t* first_bad,
+                           uint64_t* nbad, uint64_t* ngood, uint64_t* good_bytes, uint64_t* drop_bytes);
 
 /* Record assembly on the device: which physical records join into the logical records log::Reader::ReadRecord returns
  * (the loop documented at kvsep_log_accept_gaps below).  Consecutive records form a CHAIN: a record that does not

@@ -56,6 +56,7 @@
 #include "logw_run.h"
 #include "sst_run.h"
 #include "sstw_run.h"
+#include "vlog_run.h"
 
 namespace kvsep {
 
@@ -72,6 +73,7 @@ namespace kvsep {
 #include "crc32c_logframe.inc" // logw_*_kernel: the log / MANIFEST write side, records into fragments and pads
 #include "crc32c_sstindex.inc" // sst_*_kernel: the SST footer, the index-block walk, the table form's slots
 #include "crc32c_sstbuild.inc" // sst_keys_*_kernel, sstw_*_kernel: the walk with keys, the index block builder, the footer
+#include "crc32c_vlogwalk.inc" // vlog_*_kernel: the vlog header walk through an LDS window, the read form's totals
 
 }  // namespace kvsep
 
@@ -1550,6 +1552,104 @@ int kvsep_log_read_device(kvsep_crc32c_ctx* c, void* stream, const void* base, u
   const LogWalkCall w{base, n, off, len, stored, type, cap, nrec};
   return launch_log(c, s, n, true, cap, [&](Scratch& sc, bool capturing) {
     return launch_log_read_in(c, sc, s, capturing, w, acc, ok);
+  });
+}
+
+}  // extern "C"
+
+namespace {
+// ---- the value-log reader on the device (crc32c_vlogwalk.inc)
+
+struct VlogWalkCall {
+  const void* base;
+  uint64_t n;
+  uint64_t* off;
+  uint64_t* len;
+  uint32_t* stored;
+  uint64_t cap;
+  uint64_t* nrec;
+  uint64_t* consumed;
+};
+
+// The walk on `s`: one launch, no scratch.
+int launch_vlog_walk(hipStream_t s, const VlogWalkCall& w) {
+  VlogWalkArgs a{};
+  a.img = static_cast<const uint8_t*>(w.base);
+  a.n = w.n;
+  a.off = w.off, a.len = w.len, a.stored = w.stored;
+  a.cap = w.cap;
+  a.nrec = reinterpret_cast<unsigned long long*>(w.nrec);
+  a.consumed = reinterpret_cast<unsigned long long*>(w.consumed);
+  vlog_walk_kernel<<<1, vlogrun::kLanes, 0, s>>>(a);
+  KVSEP_HIP(hipGetLastError());
+  return KVSEP_OK;
+}
+
+// What the read form's checksum step needs, stated before anything is enqueued: a captured call finds all of it in its
+// capture set or is refused -- also when its cap is over what kvsep_crc32c_reserve sized the set for, which no array of
+// this form would show (the CRCs go to the caller's array).
+auto vlog_read_needs(kvsep_crc32c_ctx* c, uint64_t n, uint64_t cap, uint64_t max_len) {
+  return [=](Scratch& sc, bool capturing) {
+    if (!cap) return int(KVSEP_OK);
+    if (capturing && (!sc.verify.p || sc.vslot.cap < vslots_needed(c) || !sc.sst.holds(cap)))
+      return set_err(KVSEP_EINVAL, "a captured vlog read larger than kvsep_crc32c_reserve sized its capture set for");
+    int rc = capturing ? KVSEP_OK : ensure_verify(sc);
+    if (!rc && route_of(c, cap, n, max_len).dyn) rc = ensure_counter(sc, capturing);
+    if (!rc) rc = ensure_plan_for(c, sc, cap, n, max_len, capturing);
+    return rc;
+  };
+}
+}  // namespace
+
+extern "C" {
+
+int kvsep_vlog_walk_device(kvsep_crc32c_ctx* c, void* stream, const void* base, uint64_t n, uint64_t* off,
+                           uint64_t* len, uint32_t* stored, uint64_t cap, uint64_t* nrec, uint64_t* consumed) {
+  int rc = log_walk_args("kvsep_vlog_walk_device", c, base, n, cap, nrec);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(c->mu);
+  DeviceGuard dg(c->device);
+  KVSEP_HIP(dg.err);
+  return launch_vlog_walk(static_cast<hipStream_t>(stream), VlogWalkCall{base, n, off, len, stored, cap, nrec, consumed});
+}
+
+int kvsep_vlog_read_device(kvsep_crc32c_ctx* c, void* stream, const void* base, uint64_t n, uint64_t* off,
+                           uint64_t* len, uint32_t* stored, uint32_t* crc, uint8_t* ok, uint64_t cap,
+                           uint64_t max_len_hint, uint64_t* nrec, uint64_t* consumed, uint64_t* first_bad,
+                           uint64_t* nbad, uint64_t* ngood, uint64_t* good_bytes, uint64_t* drop_bytes) {
+  int rc = log_walk_args("kvsep_vlog_read_device", c, base, n, cap, nrec);
+  if (rc) return rc;
+  if (cap && (!off || !len || !stored || !crc))
+    return set_err(KVSEP_EINVAL, "kvsep_vlog_read_device: null off, len, stored or crc with cap != 0");
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uint64_t max_len = max_len_hint ? max_len_hint : n;
+  const VlogWalkCall w{base, n, off, len, stored, cap, nrec, consumed};
+  return with_scratch(c, s, c->sc, vlog_read_needs(c, n, cap, max_len), [&](Scratch& sc, bool capturing) -> int {
+    int r = launch_vlog_walk(s, w);
+    if (r) return r;
+    VlogTotalsArgs t{};
+    if (cap) {
+      // kvsep_crc32c_verify_device over all cap elements: the padding is an empty block whose stored word is Mask(0),
+      // which passes and is never dereferenced, so first_bad / nbad speak of records only
+      uint64_t* fb = first_bad && nbad ? first_bad : reinterpret_cast<uint64_t*>(sc.verify.p);
+      uint64_t* nb = first_bad && nbad ? nbad : reinterpret_cast<uint64_t*>(sc.verify.p + 1);
+      r = launch_batch_in(c, sc, s, capturing, base, off, len, nullptr, stored, crc, fb, nb, cap, n, max_len);
+      if (!r) r = launch_list(sc, s, capturing, crc, stored, nb, ListOut{nullptr, 0, ok}, cap);
+      if (r) return r;
+      t.first_bad_in = reinterpret_cast<const unsigned long long*>(fb);
+      t.nbad_in = reinterpret_cast<const unsigned long long*>(nb);
+    }
+    t.nrec = reinterpret_cast<const unsigned long long*>(nrec);
+    t.off = off, t.len = len, t.cap = cap;
+    t.first_bad = reinterpret_cast<unsigned long long*>(first_bad);
+    t.nbad = reinterpret_cast<unsigned long long*>(nbad);
+    t.ngood = reinterpret_cast<unsigned long long*>(ngood);
+    t.good_bytes = reinterpret_cast<unsigned long long*>(good_bytes);
+    t.drop_bytes = reinterpret_cast<unsigned long long*>(drop_bytes);
+    vlog_totals_kernel<<<1, vlogrun::kLanes, 0, s>>>(t);
+    KVSEP_HIP(hipGetLastError());
+    return KVSEP_OK;
   });
 }
 

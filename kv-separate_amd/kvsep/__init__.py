@@ -123,6 +123,10 @@ _SIGS = {
                                      [ctypes.c_uint64] + [ctypes.c_void_p] * 4),
     "kvsep_log_read_device": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 7 +
                               [ctypes.c_uint64] + [ctypes.c_void_p] * 3),
+    "kvsep_vlog_walk_device": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 3 +
+                               [ctypes.c_uint64] + [ctypes.c_void_p] * 2),
+    "kvsep_vlog_read_device": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 5 +
+                               [ctypes.c_uint64] * 2 + [ctypes.c_void_p] * 7),
     "kvsep_log_chains": (ctypes.c_uint64, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 3),
     "kvsep_log_chains_device": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_uint64] + [ctypes.c_void_p] * 6),
     "kvsep_log_records_device": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_void_p] * 7 +
@@ -590,6 +594,34 @@ class Context:
                                            _dptr(stored), _dptr(type), _dptr(ok), _dptr(accept), _dptr(gap), cap,
                                            _dptr(nrec), _dptr(dropped), _dptr(bad_length)), "kvsep_log_read_device")
         return accept
+
+    def vlog_walk_device(self, base, n, nrec, off=None, length=None, stored=None, consumed=None, cap=None,
+                         stream=None):
+        """kvsep_vlog_walk_device: the walk of vlog_walk over the n bytes of the device image at base.  nrec and
+        consumed (one-element int64 device tensors, consumed optional) receive the record count and the end of the last
+        complete record; off / length (int64) and stored (int32), each optional, are written for exactly cap elements:
+        the records first, then padding (off = length = 0, stored = mask(0)).  With no array cap is 0: the counting
+        call."""
+        if cap is None:
+            cap = min([int(t.numel()) for t in (off, length, stored) if t is not None and not isinstance(t, int)],
+                      default=0)
+        _check(lib().kvsep_vlog_walk_device(self._h, _stream_handle(stream), _dptr(base), n, _dptr(off), _dptr(length),
+                                            _dptr(stored), cap, _dptr(nrec), _dptr(consumed)), "kvsep_vlog_walk_device")
+        return nrec
+
+    def vlog_read_device(self, base, n, off, length, stored, crc, nrec, ok=None, consumed=None, first_bad=None,
+                         nbad=None, ngood=None, good_bytes=None, drop_bytes=None, cap=None, max_len_hint=0,
+                         stream=None):
+        """kvsep_vlog_read_device: vlog_walk_device, verify_device over all cap elements (the ok[] pass of the list form
+        when ok, uint8, is given) and the totals of vlog_verify_host, chained on one stream with no host step.  crc is
+        an int32 device tensor of cap elements; the result words are one-element int64 device tensors."""
+        if cap is None:
+            cap = min(int(t.numel()) for t in (off, length, stored, crc))
+        _check(lib().kvsep_vlog_read_device(self._h, _stream_handle(stream), _dptr(base), n, _dptr(off), _dptr(length),
+                                            _dptr(stored), _dptr(crc), _dptr(ok), cap, max_len_hint, _dptr(nrec),
+                                            _dptr(consumed), _dptr(first_bad), _dptr(nbad), _dptr(ngood),
+                                            _dptr(good_bytes), _dptr(drop_bytes)), "kvsep_vlog_read_device")
+        return nrec
 
     def log_chains_device(self, type, accept, nrec, first, whole, nchain, gap=None, off=None, length=None,
                           frag_off=None, frag_len=None, nwhole=None, cap=None, stream=None):
